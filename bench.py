@@ -1,7 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark: Chambolle–Pock iterations/s + L-sweep HBM GB/s (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--no-cpu] [--no-shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-shard] ...
+
+A plain run does only what the headline figure needs: it builds the problem, runs W untimed
+iterations, times exactly K, writes the final iterate if --dump-outputs is given and prints
+one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the workload).
+--full adds every other measurement to that line (the roofline, kernels, l_sweep, config4 /
+fp32_config5, sharded and cpu_baseline entries described below); --no-cpu, --no-shard,
+--no-hbm, --no-fp32 and the --shard-* / --fp32-steps / --op-reps / --cpu-seconds options
+only act together with it.
+
+--dump-outputs DIR writes what the timed call left after its last iteration, as a caller of
+raocp_cp_bench reads it back (raocp_get_primal / raocp_get_dual): DIR/primal.npy and
+DIR/dual.npy, float64, the whole vectors (|P| + |D| doubles, a few MB at config 2). The
+problem, x0 and the step size are functions of the arguments alone (recipe seed 0), so two
+builds run with the same arguments can be compared entry for entry.
 
 One step = one CP iteration (solver.py:124-161: L^T half step, prox_f with the
 dynamics sweeps and AVaR kernel projection, L half step, prox_g*, residuals and
@@ -18,7 +33,7 @@ script starts the N rank processes itself before anything touches a GPU.
   value: every rank solves its own config-2 tree instance (an MPC-style batch of
       independent problems: same tree, its own x0), no collective on the data path;
       value = total CP iterations/s of the job (weak scaling).
-  sharded: two strong-scaling legs, {"config4", "config5_fp32"}: ONE config-4 tree
+  sharded (--full): two strong-scaling legs, {"config4", "config5_fp32"}: ONE config-4 tree
       (BASELINE configs[3]: branching 3, N = 10, 88,573 nodes, nx = 32, nu = 12, fp64) and
       ONE config-5 tree (configs[4]: branching 4, N = 9, 349,525 nodes, nx = 64, nu = 16,
       fp32) whose subtrees below the replicated top are sharded across the N GPUs
@@ -32,7 +47,7 @@ torch is never imported: its wheel bundles a second ROCm runtime with the same s
 as the /opt/rocm one libraocp_hip.so links, and RCCL (dlopen'ed by the library) cannot
 initialise next to it. Barriers and the max-over-ranks go through a socket group.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline: the part of the timed CP iteration with the larger device time (the kernel after
             the dynamics sweep -- the fused k_cp3 on the benchmark trees -- or the dynamics
             projection), timed with HIP events on the context's stream over a graph of
@@ -309,6 +324,14 @@ def timed_cp(nat, x0, alpha, steps, warmup, group):
     return wall, dev_ms
 
 
+def dump_outputs(nat, out_dir):
+    """The iterate the timed call left (what raocp_get_primal / raocp_get_dual hand a caller
+    after raocp_cp_bench), whole and in float64: <out_dir>/primal.npy, <out_dir>/dual.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in (("primal", nat.get_primal()), ("dual", nat.get_dual())):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def shard_leg(args):
     """One process of a sharded solve (config 4 fp64 or config 5 fp32; a child of rank 0, see
     spawn)."""
@@ -458,6 +481,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline / kernels, L sweeps, configs 4 and 5, the sharded legs and the "
+                         "CPU baseline (the options below only act with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the iterate the timed call left as DIR/primal.npy and DIR/dual.npy (float64)")
     ap.add_argument("--op-reps", type=int, default=2000)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -508,7 +536,31 @@ def main():
     if rank != 0:
         group.barrier()  # rank 0 measures the rest; the sharded leg uses every GPU
         return 0
+    if args.dump_outputs:  # before anything else runs on this context: the timed call's iterate
+        dump_outputs(nat, args.dump_outputs)
 
+    out = {
+        "metric": METRIC, "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * wall / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[1]: i.i.d. binary scenario tree, N=12, {cache.packed.n} nodes, "
+                               f"nx={cache.packed.nx}, nu={cache.packed.nu}, AVaR 0.9, boxes +-1 "
+                               f"(SURVEY.md 8(d) config {args.config})",
+                   "nodes": cache.packed.n, "nx": cache.packed.nx, "nu": cache.packed.nu, "alpha": alpha, "tol": 0.0,
+                   "parallelism": f"replicas{world}: one independent tree instance per GPU" if world > 1 else "1 GPU"},
+        "device_ms_per_step": dev_ms / args.steps,
+    }
+    if args.full:
+        full_report(args, nat, cache, recipe, world, dev_ms, out)
+    print(json.dumps(out), flush=True)
+    if group:
+        group.barrier()
+    return 0
+
+
+def full_report(args, nat, cache, recipe, world, dev_ms, out):
+    """--full: everything the line carries beyond the headline (rank 0, after the timed call),
+    added to `out`."""
     kernels, roofline = iteration_kernels(nat, cache, 8, args.op_reps, dev_ms / args.steps)
     # L / L^T at config 2 (standalone operators, not launched by the CP iteration)
     l_sweep = {"config2": op_pair(nat, cache, 8, args.op_reps, 1)}
@@ -521,22 +573,13 @@ def main():
         legs["config5_fp32"] = fp32 = config_leg(5, "float32", args.fp32_steps, 2, 40, 2)
         l_sweep["config5_fp32"] = fp32["l_sweep"]
 
-    out = {
-        "metric": METRIC, "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * wall / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[1]: i.i.d. binary scenario tree, N=12, {cache.packed.n} nodes, "
-                               f"nx={cache.packed.nx}, nu={cache.packed.nu}, AVaR 0.9, boxes +-1 "
-                               f"(SURVEY.md 8(d) config {args.config})",
-                   "nodes": cache.packed.n, "nx": cache.packed.nx, "nu": cache.packed.nu, "alpha": alpha, "tol": 0.0,
-                   "parallelism": f"replicas{world}: one independent tree instance per GPU" if world > 1 else "1 GPU"},
-        "device_ms_per_step": dev_ms / args.steps,
+    out.update({
         "roofline": roofline,
         "kernels": kernels,
         "l_sweep": l_sweep,
         "config4": legs.get("config4"),
         "fp32_config5": fp32,
-    }
+    })
     if not args.no_shard:
         sharded = {}
         for cfg, dtype in SHARD_LEGS:
@@ -556,10 +599,6 @@ def main():
         out["sharded"] = sharded
     if not args.no_cpu and world == 1:
         out["cpu_baseline"] = cpu_baseline(recipe, args.cpu_seconds)
-    print(json.dumps(out), flush=True)
-    if group:
-        group.barrier()
-    return 0
 
 
 if __name__ == "__main__":

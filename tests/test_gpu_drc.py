@@ -193,6 +193,40 @@ def test_drc_bench_loop_matches_cp_run():
     assert np.array_equal(z_b, on.get_primal_flat())
 
 
+def test_bench_plain_run_dumps_the_timed_iterate(tmp_path):
+    """bench.py --dump-outputs: a plain run (no --full) prints the headline line alone and
+    writes the iterate its K timed iterations left, float64, bit for bit what a K-iteration
+    cp_run from the same x0 leaves; a second run with the same arguments writes the same."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K = 29
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K),
+                            "--warmup", "3", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == K and line["unit"] == "it/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+    for key in ("roofline", "kernels", "l_sweep", "config4", "fp32_config5", "sharded", "cpu_baseline"):
+        assert key not in line
+    r = recipe_config(2, seed=0)
+    cache = core.Cache(build_problem(r)[1])
+    alpha = 0.999 / cache.native.step_size()
+    assert alpha == line["config"]["alpha"]
+    st, err, _ = cache.native.cp_run(r["x0"], K - 1, 0.0, alpha)
+    assert st == 1 and err.shape[0] == K
+    for name, want in (("primal", cache.native.get_primal()), ("dual", cache.native.get_dual())):
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == want.shape
+        assert np.array_equal(got, want)
+        assert np.array_equal(got, np.load(tmp_path / "b" / (name + ".npy")))
+
+
 def test_drc_two_contexts_in_threads():
     """One active context per device: k_drc needs its whole grid resident, so the entry points
     that launch it hold a per-device lock (raocp_capi.hip SweepLock). Two threads solving on two

@@ -27,8 +27,8 @@
 #   cp6stamps   k_cp6's in-kernel stamps at config 2 (diagnostic variant build/var/diag.so)
 #   dy3trace    per-launch trace of the config-4 / config-5 dynamics (rocprofv3 kernel trace, tools/trace_seq.py)
 #   ksweep      tools/k_sweep.py: device / wall time of a benchmark call against K, graphs and eager
-#   bench20     bench.py --steps 20 --warmup 5 (the driver's K)
-#   bench       bench.py default run
+#   bench20     bench.py --full --steps 20 --warmup 5 (the driver's K)
+#   bench       bench.py --full default run
 #   prof        rocprofv3 --kernel-trace --stats of bench.py (eager launches)
 #   pmc         FETCH_SIZE / WRITE_SIZE passes of the same bench command
 #   asan        the host-ASan ABI driver on the GPU
@@ -43,7 +43,7 @@ shift
 out=gpurun_out/$tag
 mkdir -p "$out"
 PYT="python -u -m pytest -m gpu -x -v --timeout 120 --timeout-method thread"
-BARGS="--steps 96 --warmup 24 --no-cpu --no-shard --op-reps 200 --fp32-steps 12"
+BARGS="--full --steps 96 --warmup 24 --no-cpu --no-shard --op-reps 200 --fp32-steps 12"
 fail() { echo "step $1 failed"; tail -40 "$2"; exit 1; }
 for step in "$@"; do
   echo "== $step $(date +%T)"
@@ -113,9 +113,9 @@ for step in "$@"; do
             RAOCP_HIP_LIB=build/var/$v.so KS_EAGER=0 timeout -k 10 300 python -u tools/k_sweep.py > $out/k_sweep_$v.log 2>&1 || fail $step $out/k_sweep_$v.log
             echo "variant $v"; cat $out/k_sweep_$v.log
           done ;;
-    bench20) timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $out/bench_k20.log 2>&1 || fail $step $out/bench_k20.log
+    bench20) timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $out/bench_k20.log 2>&1 || fail $step $out/bench_k20.log
           tail -1 $out/bench_k20.log > $out/bench_k20.json; cut -c1-400 $out/bench_k20.json ;;
-    bench) timeout -k 10 500 python -u bench.py > $out/bench.log 2>&1 || fail $step $out/bench.log
+    bench) timeout -k 10 500 python -u bench.py --full > $out/bench.log 2>&1 || fail $step $out/bench.log
           tail -1 $out/bench.log > $out/bench.json; cut -c1-400 $out/bench.json ;;
     prof) RAOCP_EAGER=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof -o prof --output-format csv -- python3 bench.py $BARGS > $out/prof.log 2>&1 || fail $step $out/prof.log
           find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/prof_kernel_stats.csv \; ; head -30 $out/prof_kernel_stats.csv ;;
