@@ -133,7 +133,8 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * 10 fused CP iteration, 11 the CP loop's one launch of dynamics projection + CP iteration
  * (k_drc; "" when the loop runs 9 and 10 as separate launches)), as rocprofv3 reports it;
  * op 12: the forms of the k_cp5 launches ("leaf_pf=. fams=. fam_pf=.", "" when k_cp5 does not
- * run); written NUL-terminated to buf. */
+ * run); op 13: the batched CP kernel of raocp_cp_batch_run ("" when the batch runs as
+ * sequential solves); written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
 /* prox of f on the current primal (Cache.proximal_of_f, cache.py:248-257) and its steps */
@@ -170,6 +171,32 @@ int raocp_step_size(raocp_ctx* ctx, double* lambda_max, int max_it, double rtol)
  * The final iterate is left as the context's current primal/dual. */
 int raocp_cp_run(raocp_ctx* ctx, const double* x0, int max_iters, double tol, double alpha,
                  int* status, int* iters, double* err_hist, double* delta_hist);
+
+/* Batched Chambolle–Pock solves: B instances of the context's problem that share the tree,
+ * the tables and alpha and differ in x0 (and, when z0 / eta0 are given, in the starting
+ * iterate; both NULL: every instance starts from zero). Each instance runs Solver.chock's loop
+ * (solver.py:97-171) with its own stopping test. One launch runs one workgroup per instance
+ * (k_cpb, raocp_cpb.hip; chunks of RAOCP_BATCH_CHUNK iterations, default 256, until every
+ * instance is done); a context the kernel does not cover (fp32, nx > 32 or nu > 16,
+ * RAOCP_CPB=0) runs the B solves one after another through raocp_cp_run, with the same
+ * results. Outputs per instance b:
+ *   status[b]  0 converged / 1 not converged / 2 a NaN reached a box projection (that
+ *              instance stopped there; the others are not affected)
+ *   iters[b]   rows of its error caches
+ *   err_hist, delta_hist: [B][max_iters+1][3] host arrays
+ * The context's own iterate (raocp_get_primal / raocp_get_dual) and initial state are left
+ * as they were. Errors: RAOCP_ERR_ARG for B < 1, B > 4096, a NULL pointer or z0 without eta0;
+ * RAOCP_ERR_STATE on a sharded context. kernel_info op 13 names the kernel ("" when the
+ * sequential solves run). */
+int raocp_cp_batch_run(raocp_ctx* ctx, int B, const double* x0 /*[B][nx]*/,
+                       const double* z0 /*[B][P] or NULL*/, const double* eta0 /*[B][D] or NULL*/,
+                       int max_iters, double tol, double alpha,
+                       int* status /*[B]*/, int* iters /*[B]*/,
+                       double* err_hist /*[B][max_iters+1][3]*/, double* delta_hist);
+/* The final primal / dual of instance b of the last batch, in the reference's flat order. */
+int raocp_cp_batch_get(raocp_ctx* ctx, int b, double* z /*[P]*/, double* eta /*[D]*/);
+/* The root's input u_0 of every instance's final primal (what an MPC loop applies). */
+int raocp_cp_batch_first_inputs(raocp_ctx* ctx, double* u0 /*[B][nu]*/);
 
 /* Benchmark helpers (bench.py): raocp_cp_bench runs exactly `iters` CP iterations
  * (tol = 0) from (x0 at node 0, zeros) / 0 on the device, graph-replayed (whole

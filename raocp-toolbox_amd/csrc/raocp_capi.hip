@@ -7,6 +7,7 @@
 #include "raocp_dynr.h"
 #include "raocp_cp4.h"
 #include "raocp_cp5.h"
+#include "raocp_cpb.h"
 #include "../../include/raocp_hip.h"
 
 #include <dlfcn.h>
@@ -215,6 +216,23 @@ struct raocp_ctx {
     int prepared = 0;                    // raocp_cp_prepare(x0) set up a run of this many iterations
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int graph_rem_iters = 0;
+    // batched solves (raocp_cp_batch_run): the slabs and the per-instance control of k_cpb
+    // (raocp_cpb.hip), allocated once per batch size and history length and reused; a context
+    // k_cpb does not cover keeps the results of its sequential solves on the host
+    struct Batch {
+        int B = 0;                   // instances of the last batch call (0: none yet)
+        bool kernel = false;         // ... which k_cpb ran
+        int cap_B = 0;               // instances the device buffers hold
+        size_t hist_rows = 0;
+        raocp::CpbSlab lay{};
+        double* slab = nullptr;
+        Ctl* ctl = nullptr;
+        int* done = nullptr;
+        double* hist = nullptr;
+        double* u0 = nullptr;
+        std::vector<int> fk;         // final_k per instance
+        std::vector<double> hz, he, hu0;  // the sequential solves' final iterates and first inputs
+    } bt;
     std::vector<void*> allocs;
 
     template <class T>
@@ -1430,6 +1448,26 @@ int enqueue_cp_iteration(raocp_ctx* c, int it) {
     if (!defer) raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, c->redpart, c->cp_rows, 0, nullptr, nullptr);
     return RAOCP_OK;
 }
+// k_cpb (raocp_cpb.hip) covers this context's batched solves: fp64, unsharded, sizes within
+// the kernel's limits; RAOCP_CPB=0 (read at call time) selects the sequential solves
+bool cpb_on(const raocp_ctx* c) {
+    const char* e = getenv("RAOCP_CPB");
+    if (e && e[0] == '0') return false;
+    return !c->f32 && !c->comm && c->sh_R == 1 && c->nx <= raocp::kCpbMaxNx && c->nu <= raocp::kCpbMaxNu;
+}
+void batch_free(raocp_ctx* c) {
+    auto& bt = c->bt;
+    if (bt.slab) (void)hipFree(bt.slab);
+    if (bt.ctl) (void)hipFree(bt.ctl);
+    if (bt.done) (void)hipFree(bt.done);
+    if (bt.hist) (void)hipFree(bt.hist);
+    if (bt.u0) (void)hipFree(bt.u0);
+    bt.slab = bt.hist = bt.u0 = nullptr;
+    bt.ctl = nullptr;
+    bt.done = nullptr;
+    bt.cap_B = 0;
+    bt.hist_rows = 0;
+}
 // the kernel the default selection launches for op (raocp_op_bench numbering: 0 L, 1 L^T,
 // 2 dual CP kernel, 6 primal CP kernel, 9 the dynamics projection), as rocprofv3 names it
 std::string kernel_name(const raocp_ctx* c, int op) {
@@ -1495,6 +1533,8 @@ std::string kernel_name(const raocp_ctx* c, int op) {
         case 12:  // the forms of the k_cp5 launches, when they run ("" otherwise)
             if (!c->cp5) return "";
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
+        case 13:  // the batched CP kernel, when raocp_cp_batch_run launches it ("" otherwise)
+            return cpb_on(c) ? raocp::cpb_name(raocp::cpb_tab_bytes(c->dev) > 0) : "";
         case 10:
             if (c->cp6 && c->sh_S == 0) return raocp::cp6_name();
             if (c->cp5) return std::string(raocp::cp5_name(c->f32, c->nx)) + (c->sh_S > 0 ? " (+ fams x1 after X1)" : "");
@@ -2949,6 +2989,7 @@ void raocp_ctx_destroy(raocp_ctx* c) {
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (void* p : c->allocs) (void)hipFree(p);
+    batch_free(c);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3036,7 +3077,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }
@@ -3315,6 +3356,213 @@ int raocp_cp_run(raocp_ctx* c, const double* x0, int max_iters, double tol, doub
     if (status) *status = fk < max_iters ? 0 : 1;
     if (int fe = fuse_err(c)) return fe;
     if (c->h_ctl->flags & 1) return fail(RAOCP_ERR_NAN_IN_BOX, "Rectangle constraint - 'nan' value cannot be constrained");
+    return RAOCP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int batch_chunk() {
+    const char* e = getenv("RAOCP_BATCH_CHUNK");
+    const int v = e ? atoi(e) : 256;
+    return v >= 1 ? v : 256;
+}
+
+// the device buffers of a batch of B instances with `rows` history rows each
+int batch_ensure(raocp_ctx* c, int B, size_t rows) {
+    auto& bt = c->bt;
+    if (bt.cap_B == B && rows <= bt.hist_rows) return RAOCP_OK;
+    const size_t want = std::max(rows, bt.cap_B == B ? bt.hist_rows : (size_t)0);
+    batch_free(c);
+    bt.lay = raocp::cpb_layout(c->dev);
+    HIPCHK(hipMalloc((void**)&bt.slab, (size_t)B * bt.lay.stride * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&bt.ctl, (size_t)B * sizeof(Ctl)));
+    HIPCHK(hipMalloc((void**)&bt.done, (size_t)B * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&bt.hist, (size_t)B * want * 6 * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&bt.u0, (size_t)B * c->nu * sizeof(double)));
+    bt.cap_B = B;
+    bt.hist_rows = want;
+    return RAOCP_OK;
+}
+
+// rows of `width` doubles, one per instance, into the slabs at offset `off`
+int batch_scatter(raocp_ctx* c, long off, const double* src, size_t width, int B) {
+    HIPCHK(hipMemcpy2DAsync(c->bt.slab + off, (size_t)c->bt.lay.stride * sizeof(double), src, width * sizeof(double),
+                            width * sizeof(double), (size_t)B, hipMemcpyHostToDevice, c->stream));
+    return RAOCP_OK;
+}
+
+int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
+                     double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist) {
+    auto& bt = c->bt;
+    const size_t rows = (size_t)max_iters + 1;
+    int rc;
+    if ((rc = batch_ensure(c, B, rows))) return rc;
+    const raocp::CpbSlab& L = bt.lay;
+    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(bt.done, 0, (size_t)B * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(bt.u0, 0, (size_t)B * c->nu * sizeof(double), c->stream));
+    if (z0) {
+        if ((rc = batch_scatter(c, L.z[0], z0, (size_t)c->P, B))) return rc;
+        if ((rc = batch_scatter(c, L.e[0], eta0, (size_t)c->D, B))) return rc;
+    }
+    // x0 into node 0's state (cache_initial_state) and as the projection's x0bar
+    if ((rc = batch_scatter(c, L.z[0] + c->dev.X0, x0, (size_t)c->nx, B))) return rc;
+    if ((rc = batch_scatter(c, L.x0, x0, (size_t)c->nx, B))) return rc;
+    Ctl h{};
+    h.alpha = alpha;
+    h.final_k = -1;
+    h.max_iters = max_iters;
+    h.tol = tol;
+    std::vector<Ctl> hc((size_t)B, h);
+    HIPCHK(hipMemcpyAsync(bt.ctl, hc.data(), hc.size() * sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    raocp::CpbArg a{};
+    a.slab = bt.slab;
+    a.lay = L;
+    a.ctl = bt.ctl;
+    a.done = bt.done;
+    a.hist = bt.hist;
+    a.hist_rows = (long)rows;
+    a.u0 = bt.u0;
+    a.B = B;
+    a.chunk = batch_chunk();
+    a.lds_tabs = raocp::cpb_tab_bytes(c->dev) > 0 ? 1 : 0;
+    std::vector<int> hd((size_t)B, 0);
+    const long launches = (long)(rows + a.chunk - 1) / a.chunk + 1;  // every instance ends within rows iterations
+    bool all = false;
+    for (long l = 0; l < launches && !all; ++l) {
+        HIPCHK(raocp::cpb_launch(c->dev, a, c->stream));
+        HIPCHK(hipMemcpyAsync(hd.data(), bt.done, hd.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        all = std::all_of(hd.begin(), hd.end(), [](int v) { return v != 0; });
+    }
+    if (!all) return fail(RAOCP_ERR_STATE, "batched CP kernel: an instance did not finish");
+    HIPCHK(hipMemcpy(hc.data(), bt.ctl, hc.size() * sizeof(Ctl), hipMemcpyDeviceToHost));
+    std::vector<double> hh((size_t)B * rows * 6);
+    HIPCHK(hipMemcpy(hh.data(), bt.hist, hh.size() * sizeof(double), hipMemcpyDeviceToHost));
+    bt.fk.assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+        const int fk = hc[b].final_k;
+        bt.fk[b] = fk;
+        iters[b] = fk + 1;
+        status[b] = (hc[b].flags & 1) ? 2 : (fk < max_iters ? 0 : 1);
+        for (int k = 0; k <= fk; ++k)
+            for (int q = 0; q < 3; ++q) {
+                const size_t s = ((size_t)b * rows + k) * 6;
+                err_hist[((size_t)b * rows + k) * 3 + q] = hh[s + q];
+                delta_hist[((size_t)b * rows + k) * 3 + q] = hh[s + 3 + q];
+            }
+    }
+    bt.B = B;
+    bt.kernel = true;
+    return RAOCP_OK;
+}
+
+// the fallback of a context k_cpb does not cover: the B solves one after another through the
+// context's own loop, the context's iterate and initial state saved and put back
+int batch_run_seq(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
+                  double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist) {
+    auto& bt = c->bt;
+    const size_t rows = (size_t)max_iters + 1;
+    double* const sz = c->cur_z;
+    double* const se = c->cur_e;
+    const bool had_x0 = c->has_x0;
+    const std::vector<double> sx0 = c->h_x0;
+    void *kz = nullptr, *ke = nullptr;
+    HIPCHK(hipMalloc(&kz, (size_t)c->P * c->wsz + 64));
+    if (hipMalloc(&ke, (size_t)c->D * c->wsz + 64) != hipSuccess) {
+        (void)hipFree(kz);
+        return fail(RAOCP_ERR_HIP, "hipMalloc: batch fallback");
+    }
+    (void)hipMemcpyAsync(kz, sz, (size_t)c->P * c->wsz, hipMemcpyDeviceToDevice, c->stream);
+    (void)hipMemcpyAsync(ke, se, (size_t)c->D * c->wsz, hipMemcpyDeviceToDevice, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    bt.hz.assign((size_t)B * c->P, 0.0);
+    bt.he.assign((size_t)B * c->D, 0.0);
+    bt.hu0.assign((size_t)B * c->nu, 0.0);
+    bt.fk.assign(B, 0);
+    int rc = RAOCP_OK;
+    for (int b = 0; b < B && rc == RAOCP_OK; ++b) {
+        if (z0) {
+            if ((rc = raocp_set_primal(c, z0 + (size_t)b * c->P, 0))) break;
+            if ((rc = raocp_set_dual(c, eta0 + (size_t)b * c->D, 0))) break;
+        } else if ((rc = raocp_reset_iterate(c))) {
+            break;
+        }
+        rc = raocp_cp_run(c, x0 + (size_t)b * c->nx, max_iters, tol, alpha, &status[b], &iters[b],
+                          err_hist + (size_t)b * rows * 3, delta_hist + (size_t)b * rows * 3);
+        if (rc == RAOCP_ERR_NAN_IN_BOX) {
+            status[b] = 2;
+            rc = RAOCP_OK;
+        }
+        if (rc) break;
+        bt.fk[b] = iters[b] - 1;
+        if ((rc = raocp_get_primal(c, bt.hz.data() + (size_t)b * c->P, 0))) break;
+        if ((rc = raocp_get_dual(c, bt.he.data() + (size_t)b * c->D, 0))) break;
+        for (int r = 0; r < c->nu; ++r) bt.hu0[(size_t)b * c->nu + r] = bt.hz[(size_t)b * c->P + c->dev.U0 + r];
+    }
+    const std::string msg = g_err;
+    c->cur_z = sz;
+    c->cur_e = se;
+    (void)hipMemcpyAsync(sz, kz, (size_t)c->P * c->wsz, hipMemcpyDeviceToDevice, c->stream);
+    (void)hipMemcpyAsync(se, ke, (size_t)c->D * c->wsz, hipMemcpyDeviceToDevice, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(kz);
+    (void)hipFree(ke);
+    if (had_x0) (void)raocp_set_initial_state(c, sx0.data());
+    else c->has_x0 = false;
+    if (rc) return fail(rc, msg);
+    bt.B = B;
+    bt.kernel = false;
+    return RAOCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int raocp_cp_batch_run(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
+                       double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist) {
+    DevGuard dg_(c);
+    if (!c || !x0 || !status || !iters || !err_hist || !delta_hist) return fail(RAOCP_ERR_ARG, "null argument");
+    if (B < 1 || B > 4096) return fail(RAOCP_ERR_ARG, "batch size must be in 1 .. 4096");
+    if ((z0 == nullptr) != (eta0 == nullptr)) return fail(RAOCP_ERR_ARG, "z0 and eta0 are given together");
+    if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
+    if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "batched solves are not available on a sharded context");
+    c->bt.B = 0;
+    if (cpb_on(c)) return batch_run_kernel(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist);
+    return batch_run_seq(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist);
+}
+
+int raocp_cp_batch_get(raocp_ctx* c, int b, double* z, double* eta) {
+    DevGuard dg_(c);
+    if (!c || !z || !eta) return fail(RAOCP_ERR_ARG, "null argument");
+    const auto& bt = c->bt;
+    if (bt.B < 1) return fail(RAOCP_ERR_STATE, "no batch has been run");
+    if (b < 0 || b >= bt.B) return fail(RAOCP_ERR_ARG, "instance index out of range");
+    if (!bt.kernel) {
+        std::copy(bt.hz.begin() + (size_t)b * c->P, bt.hz.begin() + (size_t)(b + 1) * c->P, z);
+        std::copy(bt.he.begin() + (size_t)b * c->D, bt.he.begin() + (size_t)(b + 1) * c->D, eta);
+        return RAOCP_OK;
+    }
+    const double* slab = bt.slab + (size_t)b * bt.lay.stride;
+    const int fk = bt.fk[b];
+    HIPCHK(hipMemcpy(z, slab + bt.lay.z[(fk + 1) % 3], (size_t)c->P * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(eta, slab + bt.lay.e[(fk + 1) % 2], (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost));
+    return RAOCP_OK;
+}
+
+int raocp_cp_batch_first_inputs(raocp_ctx* c, double* u0) {
+    DevGuard dg_(c);
+    if (!c || !u0) return fail(RAOCP_ERR_ARG, "null argument");
+    const auto& bt = c->bt;
+    if (bt.B < 1) return fail(RAOCP_ERR_STATE, "no batch has been run");
+    if (!bt.kernel) {
+        std::copy(bt.hu0.begin(), bt.hu0.end(), u0);
+        return RAOCP_OK;
+    }
+    HIPCHK(hipMemcpy(u0, bt.u0, (size_t)bt.B * c->nu * sizeof(double), hipMemcpyDeviceToHost));
     return RAOCP_OK;
 }
 

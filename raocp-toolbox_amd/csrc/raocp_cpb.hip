@@ -1,0 +1,642 @@
+// raocp_cpb.hip — k_cpb: a BATCH of Chambolle–Pock solves on one small tree, as its own
+// translation unit (host interface: raocp_cpb.h).
+//
+// The instances of a batch share the tree, every table and alpha; they differ in x0 (and in
+// the starting iterate). ONE workgroup owns ONE instance and runs up to `chunk` whole CP
+// iterations of it in one launch: nothing is handed from one workgroup to another (no flag,
+// counter, spin or atomic between workgroups), every loop is bounded by `chunk`, a stage count
+// or a row count, and the phases of an iteration are separated by workgroup barriers only.
+//
+// One iteration k, with p = Z[k % 3], z-half = Z[(k + 1) % 3] (already holding the half step
+// z - alpha L^T eta with s_0 relaxed and (y, tau, s) projected on the AVaR kernel), d = E[k % 2]:
+//   1. dynamics projection of (x, u) of Z[(k + 1) % 3] in place: backward over stages N-1..0
+//      (child products [B'; A'] q_j, then d = Rinv v, q = (-x + a) + G v per node), forward
+//      0..N-1 (u = K x + d, x_j = [Abar | B][x; d]); a barrier after every phase of a stage
+//   2. dual half step v = (d + alpha L(2 z+ - p)) / alpha with the +-1/2 shifts  -> tv, and
+//      L(z+ - p) -> xi2 (one lane per dual row)
+//   3. prox of alpha g*: eta+ = alpha (v - Pi(v)) -> E[(k + 1) % 2], xi2, |xi2|, |delta2|
+//   4. next half step Z[(k + 2) % 3] = z+ - alpha L^T eta+ (s_0 -= alpha, kernel projection)
+//      together with xi0, xi1, delta0, delta1 of iteration k
+//   5. the six NaN-propagating maxima of the workgroup, the history row and the stopping test
+//      of cp_check_wave on the instance's own Ctl.
+// The arithmetic of a row is that of the node-block kernels (raocp_cp.hip) and of the per-stage
+// dynamics (raocp_dyn.hip: the same tables W, RG, KM, F of Dev with their padded row strides).
+//
+// Memory. The instance's state (three primals, two duals, xi2, v, q, d, the child products)
+// lives in its slab in HBM (CpbSlab); the slab of the main.py problem is a few KiB, so it stays
+// in the L2 of the XCD the workgroup runs on. The tables every instance shares (sqrt Q, sqrt R,
+// sqrt Pf, the box bounds) are staged in LDS once per launch when they fit kCpbLdsTabs.
+
+#include "raocp_cpb.h"
+
+namespace raocp {
+namespace {
+
+typedef const glbd* cgd;
+typedef const ldsd* cld;
+typedef __attribute__((address_space(1))) const int glbi;
+
+constexpr __host__ __device__ int rup_(int a, int b) { return (a + b - 1) / b * b; }
+// the row strides of the dynamics tables (raocp_dyn.hip tstride)
+constexpr __host__ __device__ int tstride_(int k) { return (k / 2) % 2 == 0 ? k + 2 : k; }
+
+__device__ __forceinline__ int e3(const Dev& p, int j) { return p.E3 + 1 + (j - 1) * p.nx; }
+__device__ __forceinline__ int e4(const Dev& p, int j) { return p.E4 + 1 + (j - 1) * p.nu; }
+__device__ __forceinline__ int e11(const Dev& p, int l) { return p.E11 + p.m + (l - p.m) * p.nx; }
+
+// SecondOrderCone.project (cones.py:113-132) for one coordinate of the block
+__device__ __forceinline__ double soc_apply(double v, bool is_t, double nf, double t) {
+    if (nf <= t) return v;
+    if (nf <= -t) return 0.0;
+    const double s = (nf + t) / 2.0;
+    return is_t ? s : s * (v / nf);
+}
+// Rectangle._constrain (rectangle.py:50-59); a NaN stays and raises the lane's flag
+__device__ __forceinline__ double box_apply(double v, double lo, double hi, bool& nan) {
+    if (lo <= v && v <= hi) return v;
+    if (v <= lo) return lo;
+    if (v >= hi) return hi;
+    nan = true;
+    return v;
+}
+
+// the tables every instance shares, in LDS (PT = cld) or in HBM (PT = cgd)
+template <class PT>
+struct Tabs {
+    PT SQ, SR, SP, BLn, BHn, BLl, BHl;
+};
+
+// one instance's arrays for iteration k
+struct View {
+    glbd* pz;   // p = Z[k % 3]
+    glbd* zp;   // z+ = Z[(k + 1) % 3]
+    glbd* out;  // Z[(k + 2) % 3]
+    glbd* d;    // E[k % 2]
+    glbd* eo;   // eta+ = E[(k + 1) % 2]
+    glbd* xi2;
+    glbd* tv;
+    glbd* q;
+    glbd* dd;
+    glbd* pb;
+    cgd x0;
+};
+
+struct Maxima {
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0, m5 = 0.0;
+    // one primal entry: pp = p, zz = z+, w = L^T(d - eta+), lc = L^T xi2
+    __device__ __forceinline__ void account(double alpha, double pp, double zz, double w, double lc) {
+        const double x1 = (pp - zz) / alpha - w;
+        const double x0v = x1 + lc;
+        const double dl1 = zz - pp;
+        const double dl0 = dl1 + w;
+        m0 = nmax(m0, fabs(x0v));
+        m1 = nmax(m1, fabs(x1));
+        m3 = nmax(m3, fabs(dl0));
+        m4 = nmax(m4, fabs(dl1));
+    }
+};
+
+// ---- the primal half step from the dual dA (FULL: eta+, with the residuals of the iteration;
+// else the solve's first half step from d): src - alpha L^T dA, s_0 -= alpha, kernel projection
+template <bool FULL, class PT>
+__device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, const View& v, glbd* out, double alpha,
+                                             Maxima& mx, int tid, int nthr) {
+    const int nx = p.nx, nu = p.nu, R = nx + nu;
+    cgd pz = v.pz;
+    cgd src = FULL ? v.zp : v.pz;
+    cgd dA = FULL ? v.eo : v.d;
+    cgd dP = v.d;
+    cgd xg = v.xi2;
+    glbrec* frec = (glbrec*)p.frec;
+    glbrec* crec = (glbrec*)p.crec;
+    glbrec* lrec = (glbrec*)p.lrec;
+    // x / u rows of the nonleaf nodes: sum over children of sqrtQ_j eta3_j (sqrtR_j eta4_j) + eta7
+    for (int it = tid; it < p.m * R; it += nthr) {
+        const int i = it / R, r = it - i * R;
+        const bool isx = r < nx;
+        const int rr = isx ? r : r - nx;
+        const Rec fr = frec[i];
+        double accA = 0.0, accW = 0.0, accC = 0.0;
+        if (fr.w >= 0) {
+            const int o = fr.w + r;
+            accA = dA[o];
+            if (FULL) {
+                accW = dP[o] - dA[o];
+                accC = xg[o];
+            }
+        }
+        for (int q = 0; q < fr.y; ++q) {
+            const int j = fr.z + q;
+            const Rec cr = crec[j];
+            const int len = isx ? nx : nu;
+            const PT M = isx ? tb.SQ + (size_t)cr.y * nx * nx + rr : tb.SR + (size_t)cr.z * nu * nu + rr;
+            const int o = isx ? e3(p, j) : e4(p, j);
+            double sA = 0.0, sW = 0.0, sC = 0.0;
+            for (int k = 0; k < len; ++k) {
+                const double mk = M[k * len], va = dA[o + k];
+                sA = fma(mk, va, sA);
+                if (FULL) {
+                    sW = fma(mk, dP[o + k] - va, sW);
+                    sC = fma(mk, xg[o + k], sC);
+                }
+            }
+            accA += sA;
+            accW += sW;
+            accC += sC;
+        }
+        const int e = isx ? p.X0 + i * nx + rr : p.U0 + i * nu + rr;
+        const double zz = src[e];
+        out[e] = zz - alpha * accA;
+        if (FULL) mx.account(alpha, pz[e], zz, accW, accC);
+    }
+    // x rows of the leaves: sqrtPf eta11 + eta14
+    for (int it = tid; it < (p.n - p.m) * nx; it += nthr) {
+        const int ll = it / nx, r = it - ll * nx, l = p.m + ll;
+        const Rec lr = lrec[ll];
+        const PT M = tb.SP + (size_t)lr.x * nx * nx + r;
+        const int o = e11(p, l);
+        double sA = 0.0, sW = 0.0, sC = 0.0;
+        for (int k = 0; k < nx; ++k) {
+            const double mk = M[k * nx], va = dA[o + k];
+            sA = fma(mk, va, sA);
+            if (FULL) {
+                sW = fma(mk, dP[o + k] - va, sW);
+                sC = fma(mk, xg[o + k], sC);
+            }
+        }
+        if (lr.z >= 0) {
+            const int q = lr.z + r;
+            sA += dA[q];
+            if (FULL) {
+                sW += dP[q] - dA[q];
+                sC += xg[q];
+            }
+        }
+        const int e = p.X0 + l * nx + r;
+        const double zz = src[e];
+        out[e] = zz - alpha * sA;
+        if (FULL) mx.account(alpha, pz[e], zz, sW, sC);
+    }
+    // (y_i, tau_j, s_j) of one nonleaf node per lane: L^T, the root's s_0 relaxation and the
+    // closed-form AVaR kernel projection (k_kernel_proj); the half-step values wait in `out`
+    for (int i = tid; i < p.m; i += nthr) {
+        const Rec fr = frec[i];
+        const int c = fr.y, cs = fr.z, yo = p.Y0 + fr.x, e1o = p.E1 + fr.x;
+        const double al = ((cgd)p.alpha_r)[i];
+        const double e2A = dA[p.E2 + i];
+        double e2W = 0.0, e2C = 0.0;
+        if (FULL) {
+            e2W = dP[p.E2 + i] - e2A;
+            e2C = xg[p.E2 + i];
+        }
+        const int f2 = 2 * c;
+        double y2c = src[yo + f2] - alpha * (dA[e1o + f2] - 1.0 * e2A);
+        if (FULL) mx.account(alpha, pz[yo + f2], src[yo + f2], (dP[e1o + f2] - dA[e1o + f2]) - 1.0 * e2W, xg[e1o + f2] - 1.0 * e2C);
+        if (i == 0) {
+            const double z0s = src[p.S0];
+            out[p.S0] = (z0s - alpha * e2A) - alpha;
+            if (FULL) mx.account(alpha, pz[p.S0], z0s, e2W, e2C);
+        }
+        double sr = 0.0;
+        for (int q = 0; q < c; ++q) {
+            const int j = cs + q, f0 = q, f1 = c + q;
+            const double b = ((cgd)p.cond)[j];
+            const double lt0 = dA[e1o + f0] - b * e2A, lt1 = dA[e1o + f1] - 0.0 * e2A;
+            const double v0 = src[yo + f0] - alpha * lt0;
+            const double v1 = src[yo + f1] - alpha * lt1;
+            const double ltt = 0.5 * (dA[p.E5 + j] + dA[p.E6 + j]);
+            const double v2 = src[p.T0 + j] - alpha * ltt;
+            const double lts = j < p.m ? dA[p.E2 + j] : 0.5 * (dA[p.E12 + j] + dA[p.E13 + j]);
+            const double v3 = src[p.S0 + j] - alpha * lts;
+            if (FULL) {
+                const double w0 = (dP[e1o + f0] - dA[e1o + f0]) - b * e2W, c0 = xg[e1o + f0] - b * e2C;
+                const double w1 = (dP[e1o + f1] - dA[e1o + f1]) - 0.0 * e2W, c1 = xg[e1o + f1] - 0.0 * e2C;
+                const double wt = 0.5 * ((dP[p.E5 + j] - dA[p.E5 + j]) + (dP[p.E6 + j] - dA[p.E6 + j]));
+                const double ct = 0.5 * (xg[p.E5 + j] + xg[p.E6 + j]);
+                double ws, cs2;
+                if (j < p.m) {
+                    ws = dP[p.E2 + j] - dA[p.E2 + j];
+                    cs2 = xg[p.E2 + j];
+                } else {
+                    ws = 0.5 * ((dP[p.E12 + j] - dA[p.E12 + j]) + (dP[p.E13 + j] - dA[p.E13 + j]));
+                    cs2 = 0.5 * (xg[p.E12 + j] + xg[p.E13 + j]);
+                }
+                mx.account(alpha, pz[yo + f0], src[yo + f0], w0, c0);
+                mx.account(alpha, pz[yo + f1], src[yo + f1], w1, c1);
+                mx.account(alpha, pz[p.T0 + j], src[p.T0 + j], wt, ct);
+                mx.account(alpha, pz[p.S0 + j], src[p.S0 + j], ws, cs2);
+            }
+            out[yo + f0] = v0;
+            out[yo + f1] = v1;
+            out[p.T0 + j] = v2;
+            out[p.S0 + j] = v3;
+            sr += al * v0 - v1 + y2c - v2 - v3;
+        }
+        const double a = al * al + 3.0;
+        double sw = 0.0;
+        for (int q = 0; q < c; ++q) {
+            const int j = cs + q, f0 = q, f1 = c + q;
+            const double v0 = out[yo + f0], v1 = out[yo + f1], v2 = out[p.T0 + j], v3 = out[p.S0 + j];
+            const double rk = al * v0 - v1 + y2c - v2 - v3;
+            const double w = (rk - sr / (a + (double)c)) / a;
+            out[yo + f0] = v0 - al * w;
+            out[yo + f1] = v1 + w;
+            out[p.T0 + j] = v2 + w;
+            out[p.S0 + j] = v3 + w;
+            sw += w;
+        }
+        out[yo + f2] = y2c - sw;
+    }
+}
+
+// ---- projection of (x, u) of z onto the dynamics (cache.py:259-288), stage by stage
+__device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd* z, int tid, int nthr) {
+    const int nx = p.nx, nu = p.nu, R = nx + nu;
+    const int SKP = tstride_(rup_(nx, 8)), SKF = tstride_(rup_(nx + nu, 8)), SNU = tstride_(rup_(nu, 2));
+    glbrec* ninfo = (glbrec*)p.ninfo;
+    glbrec* cinfo = (glbrec*)p.cinfo;
+    glbi* sp = (glbi*)p.stage_ptr;
+    cgd W = (cgd)p.dW, RG = (cgd)p.dRG, KM = (cgd)p.dKM, F = (cgd)p.dF;
+    for (int t = p.N - 1; t >= 0; --t) {
+        const int b = sp[t], e = min((int)sp[t + 1], p.m);
+        if (b >= e) continue;  // uniform over the workgroup
+        const Rec nb = ninfo[b], ne = ninfo[e - 1];
+        const int cb = nb.x, ce = ne.x + ne.y;
+        // child products [h | a]_j = sign [B'; A'] q_j (a leaf child: q_j = -x_j)
+        for (int it = tid; it < (ce - cb) * R; it += nthr) {
+            const int jj = it / R, rho = it - jj * R, j = cb + jj;
+            const Rec cj = cinfo[j];
+            cgd w = W + ((size_t)cj.x * R + rho) * SKP;
+            cgd qv = j < p.m ? (cgd)v.q + (size_t)j * nx : (cgd)z + p.X0 + (size_t)j * nx;
+            double acc = 0.0;
+            for (int k = 0; k < nx; ++k) acc = fma(w[k], qv[k], acc);
+            v.pb[(size_t)j * R + rho] = j < p.m ? acc : -acc;
+        }
+        __syncthreads();
+        // d = Rinv v, q = (-x + a) + G v with v = u - sum_j h_j
+        for (int it = tid; it < (e - b) * R; it += nthr) {
+            const int ii = it / R, tr = it - ii * R, i = b + ii;
+            const Rec ni = ninfo[i];
+            cgd rg = RG + ((size_t)ni.z * R + tr) * SNU;
+            cgd u = (cgd)z + p.U0 + (size_t)i * nu;
+            double s = 0.0;
+            for (int k = 0; k < nu; ++k) {
+                double vk = u[k];
+                for (int q = 0; q < ni.y; ++q) vk -= v.pb[(size_t)(ni.x + q) * R + k];
+                s = fma(rg[k], vk, s);
+            }
+            if (tr < nu) {
+                v.dd[(size_t)i * nu + tr] = s;
+            } else {
+                const int r = tr - nu;
+                double a = 0.0;
+                for (int q = 0; q < ni.y; ++q) a += v.pb[(size_t)(ni.x + q) * R + nu + r];
+                v.q[(size_t)i * nx + r] = (-z[p.X0 + (size_t)i * nx + r] + a) + s;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < nx) z[p.X0 + tid] = v.x0[tid];  // x_0 = x0bar (cache.py:282)
+    __syncthreads();
+    for (int t = 0; t < p.N; ++t) {
+        const int b = sp[t], e = min((int)sp[t + 1], p.m);
+        if (b >= e) continue;
+        const Rec nb = ninfo[b], ne = ninfo[e - 1];
+        const int cb = nb.x, ce = ne.x + ne.y;
+        const int nU = (e - b) * nu, nX = (ce - cb) * nx;
+        for (int it = tid; it < nU + nX; it += nthr) {
+            if (it < nU) {
+                const int ii = it / nu, r = it - ii * nu, i = b + ii;
+                const Rec ni = ninfo[i];
+                cgd km = KM + ((size_t)ni.z * nu + r) * SKP;
+                cgd x = (cgd)z + p.X0 + (size_t)i * nx;
+                double s = 0.0;
+                for (int k = 0; k < nx; ++k) s = fma(km[k], x[k], s);
+                z[p.U0 + (size_t)i * nu + r] = s + v.dd[(size_t)i * nu + r];
+            } else {
+                const int wi = it - nU, jj = wi / nx, r = wi - jj * nx, j = cb + jj;
+                const Rec cj = cinfo[j];
+                cgd f = F + ((size_t)cj.y * nx + r) * SKF;
+                cgd x = (cgd)z + p.X0 + (size_t)cj.z * nx;
+                cgd dv = (cgd)v.dd + (size_t)cj.z * nu;
+                double s = 0.0;
+                for (int k = 0; k < nx; ++k) s = fma(f[k], x[k], s);
+                for (int k = 0; k < nu; ++k) s = fma(f[nx + k], dv[k], s);
+                z[p.X0 + (size_t)j * nx + r] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the dual rows. PASS 1: v = (d + alpha L(2 z+ - p)) / alpha (+-1/2) -> tv, L(z+ - p) -> xi2.
+// PASS 2: eta+ = alpha (v - Pi(v)) -> eo, xi2 = (d - eta+) / alpha + L(z+ - p), |xi2|, |delta2|.
+// Rows: per child j >= 1 eta3 (nx), eta4 (nu), eta5, eta6 (one SOC); per nonleaf i eta1
+// (2c + 1), eta2, eta7 (nx + nu, a box when the node has one); per leaf eta11 (nx), eta12,
+// eta13 (one SOC), eta14 (nx, a box when the leaf has one).
+template <int PASS, class PT>
+__device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, const View& v, double alpha, Maxima& mx,
+                                           bool& nan, int tid, int nthr) {
+    const int nx = p.nx, nu = p.nu;
+    cgd pz = v.pz, zp = v.zp, d = v.d;
+    glbrec* frec = (glbrec*)p.frec;
+    glbrec* crec = (glbrec*)p.crec;
+    glbrec* lrec = (glbrec*)p.lrec;
+    auto put = [&](int e, double av, double bb, double shift) {
+        const double vv = (d[e] + alpha * av) / alpha + shift;
+        v.tv[e] = vv;
+        v.xi2[e] = bb;
+    };
+    auto finish = [&](int e, double vv, double pv) {
+        const double dv = d[e], bb = v.xi2[e];
+        const double ep = alpha * (vv - pv);
+        v.eo[e] = ep;
+        const double x2 = (dv - ep) / alpha + bb;
+        v.xi2[e] = x2;
+        mx.m2 = nmax(mx.m2, fabs(x2));
+        mx.m5 = nmax(mx.m5, fabs(ep - dv));
+    };
+    const int GC = nx + nu + 2;
+    for (int it = tid; it < (p.n - 1) * GC; it += nthr) {
+        const int jj = it / GC, r = it - jj * GC, j = 1 + jj;
+        const int e = r < nx ? e3(p, j) + r : (r < nx + nu ? e4(p, j) + r - nx : (r == nx + nu ? p.E5 : p.E6) + j);
+        if (PASS == 1) {
+            const Rec cr = crec[j];
+            double av, bb, shift = 0.0;
+            if (r < nx + nu) {
+                const bool isx = r < nx;
+                const int rr = isx ? r : r - nx, len = isx ? nx : nu;
+                const PT M = isx ? tb.SQ + (size_t)cr.y * nx * nx + rr : tb.SR + (size_t)cr.z * nu * nu + rr;
+                const int o = isx ? p.X0 + cr.x * nx : p.U0 + cr.x * nu;
+                double sa = 0.0, sb = 0.0;
+                for (int k = 0; k < len; ++k) {
+                    const double mk = M[k * len], zk = zp[o + k], pk = pz[o + k];
+                    sa = fma(mk, 2.0 * zk - pk, sa);
+                    sb = fma(mk, zk - pk, sb);
+                }
+                av = sa;
+                bb = sb;
+            } else {
+                const double zt = zp[p.T0 + j], pt = pz[p.T0 + j];
+                av = 0.5 * (2.0 * zt - pt);
+                bb = 0.5 * (zt - pt);
+                shift = r == nx + nu ? -0.5 : 0.5;
+            }
+            put(e, av, bb, shift);
+        } else {
+            double ss = 0.0;
+            const int o3 = e3(p, j), o4 = e4(p, j);
+            for (int q = 0; q < nx; ++q) ss += v.tv[o3 + q] * v.tv[o3 + q];
+            for (int q = 0; q < nu; ++q) ss += v.tv[o4 + q] * v.tv[o4 + q];
+            ss += v.tv[p.E5 + j] * v.tv[p.E5 + j];
+            const double vv = v.tv[e];
+            finish(e, vv, soc_apply(vv, r == GC - 1, sqrt(ss), v.tv[p.E6 + j]));
+        }
+    }
+    const int GP = 2 * p.cmax + 2 + nx + nu;
+    for (int it = tid; it < p.m * GP; it += nthr) {
+        const int i = it / GP, r = it - i * GP;
+        const Rec fr = frec[i];
+        const int c = fr.y, yo = p.Y0 + fr.x, cs = fr.z;
+        if (r < 2 * c + 1) {
+            const int e = p.E1 + fr.x + r;
+            if (PASS == 1) {
+                const double zy = zp[yo + r], py = pz[yo + r];
+                put(e, 2.0 * zy - py, zy - py, 0.0);
+            } else {
+                const double vv = v.tv[e];
+                finish(e, vv, r < 2 * c ? fmax(vv, 0.0) : vv);
+            }
+        } else if (r == 2 * p.cmax + 1) {
+            const int e = p.E2 + i;
+            if (PASS == 1) {
+                double bya = 0.0, byb = 0.0;
+                for (int k = 0; k < c; ++k) {
+                    const double cp = ((cgd)p.cond)[cs + k];
+                    bya = fma(cp, 2.0 * zp[yo + k] - pz[yo + k], bya);
+                    byb = fma(cp, zp[yo + k] - pz[yo + k], byb);
+                }
+                bya += 2.0 * zp[yo + 2 * c] - pz[yo + 2 * c];
+                byb += zp[yo + 2 * c] - pz[yo + 2 * c];
+                const double zs = zp[p.S0 + i], ps = pz[p.S0 + i];
+                put(e, (2.0 * zs - ps) - bya, (zs - ps) - byb, 0.0);
+            } else {
+                const double vv = v.tv[e];
+                finish(e, vv, fmax(vv, 0.0));
+            }
+        } else if (r >= 2 * p.cmax + 2 && fr.w >= 0) {
+            const int rr = r - (2 * p.cmax + 2);
+            const int e = fr.w + rr;
+            if (PASS == 1) {
+                const int o = rr < nx ? p.X0 + i * nx + rr : p.U0 + i * nu + rr - nx;
+                const double zv = zp[o], pv = pz[o];
+                put(e, 2.0 * zv - pv, zv - pv, 0.0);
+            } else {
+                const int bi = ((glbi*)p.iBnl)[i];
+                const double vv = v.tv[e];
+                finish(e, vv, box_apply(vv, tb.BLn[(size_t)bi * (nx + nu) + rr], tb.BHn[(size_t)bi * (nx + nu) + rr], nan));
+            }
+        }
+    }
+    const int GL = 2 * nx + 2;
+    for (int it = tid; it < (p.n - p.m) * GL; it += nthr) {
+        const int ll = it / GL, r = it - ll * GL, l = p.m + ll;
+        const Rec lr = lrec[ll];
+        if (r < nx + 2) {
+            const int e = r < nx ? e11(p, l) + r : (r == nx ? p.E12 : p.E13) + l;
+            if (PASS == 1) {
+                double av, bb, shift = 0.0;
+                if (r < nx) {
+                    const PT M = tb.SP + (size_t)lr.x * nx * nx + r;
+                    const int o = p.X0 + l * nx;
+                    double sa = 0.0, sb = 0.0;
+                    for (int k = 0; k < nx; ++k) {
+                        const double mk = M[k * nx], zk = zp[o + k], pk = pz[o + k];
+                        sa = fma(mk, 2.0 * zk - pk, sa);
+                        sb = fma(mk, zk - pk, sb);
+                    }
+                    av = sa;
+                    bb = sb;
+                } else {
+                    const double zs = zp[p.S0 + l], ps = pz[p.S0 + l];
+                    av = 0.5 * (2.0 * zs - ps);
+                    bb = 0.5 * (zs - ps);
+                    shift = r == nx ? -0.5 : 0.5;
+                }
+                put(e, av, bb, shift);
+            } else {
+                double ss = 0.0;
+                const int o11 = e11(p, l);
+                for (int q = 0; q < nx; ++q) ss += v.tv[o11 + q] * v.tv[o11 + q];
+                ss += v.tv[p.E12 + l] * v.tv[p.E12 + l];
+                const double vv = v.tv[e];
+                finish(e, vv, soc_apply(vv, r == nx + 1, sqrt(ss), v.tv[p.E13 + l]));
+            }
+        } else if (lr.z >= 0) {
+            const int rr = r - nx - 2;
+            const int e = lr.z + rr;
+            if (PASS == 1) {
+                const double zv = zp[p.X0 + l * nx + rr], pv = pz[p.X0 + l * nx + rr];
+                put(e, 2.0 * zv - pv, zv - pv, 0.0);
+            } else {
+                const double vv = v.tv[e];
+                finish(e, vv, box_apply(vv, tb.BLl[(size_t)lr.y * nx + rr], tb.BHl[(size_t)lr.y * nx + rr], nan));
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ View view_of(double* slab, const CpbSlab& L, int k) {
+    View v;
+    v.pz = (glbd*)(slab + L.z[k % 3]);
+    v.zp = (glbd*)(slab + L.z[(k + 1) % 3]);
+    v.out = (glbd*)(slab + L.z[(k + 2) % 3]);
+    v.d = (glbd*)(slab + L.e[k % 2]);
+    v.eo = (glbd*)(slab + L.e[(k + 1) % 2]);
+    v.xi2 = (glbd*)(slab + L.xi2);
+    v.tv = (glbd*)(slab + L.tv);
+    v.q = (glbd*)(slab + L.q);
+    v.dd = (glbd*)(slab + L.dd);
+    v.pb = (glbd*)(slab + L.pb);
+    v.x0 = (cgd)(slab + L.x0);
+    return v;
+}
+
+template <class PT>
+__device__ __forceinline__ void cpb_body(const Dev& p, const CpbArg& a, const Tabs<PT>& tb, int b) {
+    __shared__ double s_red[6][kCpbBlock / 64];
+    __shared__ int s_ctl[2];  // {done, k} of the instance, as thread 0 left them
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    Ctl* ctl = a.ctl + b;
+    double* slab = a.slab + (size_t)b * a.lay.stride;
+    double* hist = a.hist + (size_t)b * a.hist_rows * 6;
+    const double alpha = ctl->alpha;
+    int k = ctl->k;
+    if (!ctl->pad) {
+        // the solve's first half step Z[1] = prox-part(Z[0] - alpha L^T E[0])
+        const View v = view_of(slab, a.lay, 0);
+        Maxima none;
+        primal_phase<false>(p, tb, v, v.zp, alpha, none, tid, nthr);
+        __syncthreads();
+        if (tid == 0) ctl->pad = 1;
+    }
+    for (int it = 0; it < a.chunk; ++it) {
+        const View v = view_of(slab, a.lay, k);
+        Maxima mx;
+        bool nan = false;
+        dynamics_phase(p, v, v.zp, tid, nthr);
+        dual_phase<1>(p, tb, v, alpha, mx, nan, tid, nthr);
+        __syncthreads();
+        dual_phase<2>(p, tb, v, alpha, mx, nan, tid, nthr);
+        __syncthreads();
+        primal_phase<true>(p, tb, v, v.out, alpha, mx, tid, nthr);
+        // the six maxima of the instance, its history row and the stopping test (cp_check_wave)
+        const double mm[6] = {wave_max(mx.m0), wave_max(mx.m1), wave_max(mx.m2),
+                              wave_max(mx.m3), wave_max(mx.m4), wave_max(mx.m5)};
+        if ((tid & 63) == 0) _Pragma("unroll") for (int q = 0; q < 6; ++q) s_red[q][tid >> 6] = mm[q];
+        const int any_nan = __syncthreads_or(nan ? 1 : 0);
+        if (tid == 0) {
+            double m[6];
+            _Pragma("unroll") for (int q = 0; q < 6; ++q) {
+                double r = s_red[q][0];
+                for (int w = 1; w < (nthr >> 6); ++w) r = nmax(r, s_red[q][w]);
+                m[q] = r;
+                hist[(size_t)k * 6 + q] = r;
+            }
+            const double err = nmax(nmax(m[0], m[1]), m[2]);
+            int done = 0;
+            if (any_nan) ctl->flags |= 1;
+            if (k >= ctl->max_iters || err <= ctl->tol || any_nan) {
+                ctl->done = 1;
+                ctl->final_k = k;
+                a.done[b] = 1;
+                done = 1;
+            } else {
+                ctl->k = k + 1;
+            }
+            s_ctl[0] = done;
+            s_ctl[1] = done ? k : k + 1;
+        }
+        __syncthreads();
+        const int done = s_ctl[0];
+        k = s_ctl[1];
+        if (done) {
+            if (tid < p.nu) a.u0[(size_t)b * p.nu + tid] = v.zp[p.U0 + tid];
+            break;
+        }
+    }
+}
+
+template <bool LT>
+__global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
+    extern __shared__ __attribute__((aligned(16))) double smem_[];
+    const int b = blockIdx.x;
+    if (b >= a.B || a.ctl[b].done) return;  // a finished instance leaves at kernel entry
+    const int nx = p.nx, nu = p.nu;
+    const int nQ = p.nSQ * nx * nx, nR = p.nSR * nu * nu, nP = p.nSP * nx * nx, nBn = p.nBnl * (nx + nu), nBl = p.nBl * nx;
+    if constexpr (LT) {
+        ldsd* s = (ldsd*)smem_;
+        const cgd src[7] = {(cgd)p.SQ, (cgd)p.SR, (cgd)p.SP, (cgd)p.blo_nl, (cgd)p.bhi_nl, (cgd)p.blo_l, (cgd)p.bhi_l};
+        const int cnt[7] = {nQ, nR, nP, nBn, nBn, nBl, nBl};
+        int off[8];
+        off[0] = 0;
+        _Pragma("unroll") for (int t = 0; t < 7; ++t) off[t + 1] = off[t] + cnt[t];
+        _Pragma("unroll") for (int t = 0; t < 7; ++t)
+            for (int e = threadIdx.x; e < cnt[t]; e += blockDim.x) s[off[t] + e] = src[t][e];
+        __syncthreads();
+        const Tabs<cld> tb{s + off[0], s + off[1], s + off[2], s + off[3], s + off[4], s + off[5], s + off[6]};
+        cpb_body(p, a, tb, b);
+    } else {
+        const Tabs<cgd> tb{(cgd)p.SQ, (cgd)p.SR, (cgd)p.SP, (cgd)p.blo_nl, (cgd)p.bhi_nl, (cgd)p.blo_l, (cgd)p.bhi_l};
+        cpb_body(p, a, tb, b);
+    }
+}
+
+long tab_doubles(const Dev& p) {
+    return (long)p.nSQ * p.nx * p.nx + (long)p.nSR * p.nu * p.nu + (long)p.nSP * p.nx * p.nx +
+           2L * p.nBnl * (p.nx + p.nu) + 2L * p.nBl * p.nx;
+}
+
+}  // namespace
+
+CpbSlab cpb_layout(const Dev& p) {
+    CpbSlab L{};
+    long at = 0;
+    auto take = [&](long count) {
+        const long o = at;
+        at += (count + 1) / 2 * 2;
+        return o;
+    };
+    for (int b = 0; b < 3; ++b) L.z[b] = take(p.P);
+    for (int b = 0; b < 2; ++b) L.e[b] = take(p.D);
+    L.xi2 = take(p.D);
+    L.tv = take(p.D);
+    L.q = take((long)p.n * p.nx);
+    L.dd = take((long)p.m * p.nu);
+    L.pb = take((long)p.n * (p.nx + p.nu));
+    L.x0 = take(p.nx);
+    L.stride = (at + 31) / 32 * 32;
+    return L;
+}
+
+size_t cpb_tab_bytes(const Dev& p) {
+    const long b = tab_doubles(p) * (long)sizeof(double);
+    return b <= kCpbLdsTabs ? (size_t)b : 0;
+}
+
+hipError_t cpb_launch(const Dev& p, const CpbArg& a, hipStream_t stream) {
+    if (a.lds_tabs)
+        k_cpb<true><<<a.B, kCpbBlock, tab_doubles(p) * sizeof(double), stream>>>(p, a);
+    else
+        k_cpb<false><<<a.B, kCpbBlock, 0, stream>>>(p, a);
+    return hipGetLastError();
+}
+
+const char* cpb_name(bool lds_tabs) { return lds_tabs ? "k_cpb<true>" : "k_cpb<false>"; }
+
+}  // namespace raocp

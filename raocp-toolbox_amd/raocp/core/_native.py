@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "raocp_device_synchronize", "raocp_debug_dyn_stamps",
     "raocp_shard_setup", "raocp_shard_owned", "raocp_comm_unique_id", "raocp_comm_init", "raocp_group_cp_run",
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
+    "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs",
 ]
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -94,6 +95,9 @@ def load_library():
         "raocp_step_size": (c_int, [vp, _f64p, c_int, c_double]),
         "raocp_cp_run": (c_int, [vp, vp, c_int, c_double, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                  vp, vp]),
+        "raocp_cp_batch_run": (c_int, [vp, c_int, vp, vp, vp, c_int, c_double, c_double, vp, vp, vp, vp]),
+        "raocp_cp_batch_get": (c_int, [vp, c_int, vp, vp]),
+        "raocp_cp_batch_first_inputs": (c_int, [vp, vp]),
         "raocp_cp_prepare": (c_int, [vp, vp, c_int, c_double]),
         "raocp_cp_bench": (c_int, [vp, vp, c_int, c_double, ctypes.POINTER(ctypes.c_float)]),
         "raocp_op_bench": (c_int, [vp, c_int, c_int, ctypes.POINTER(ctypes.c_float)]),
@@ -328,6 +332,49 @@ class NativeContext:
                                            ctypes.byref(status), ctypes.byref(iters), _ptr(err), _ptr(derr)))
         k = iters.value
         return status.value, err[:k].copy(), derr[:k].copy()
+
+    def cp_batch_run(self, x0, max_iters, tol, alpha, z0=None, eta0=None):
+        """B CP solves that share the problem and alpha: x0 is (B, nx); z0 (B, P) and eta0
+        (B, D) are the starting iterates (both None: zeros). Returns (status[B] with 0 / 1 and
+        2 = NaN in a box, [error_cache], [delta_error_cache]), one (rows, 3) array per instance."""
+        self._require_l()
+        nx = self._packed.nx
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
+        if x0.ndim != 2 or x0.shape[1] != nx:
+            raise ValueError(f"initial states of shape {x0.shape}, expected (B, {nx})")
+        B = x0.shape[0]
+        if (z0 is None) != (eta0 is None):
+            raise ValueError("z0 and eta0 are given together")
+        if z0 is not None:
+            z0 = np.ascontiguousarray(np.asarray(z0, dtype=np.float64))
+            eta0 = np.ascontiguousarray(np.asarray(eta0, dtype=np.float64))
+            if z0.shape != (B, self.P) or eta0.shape != (B, self.D):
+                raise ValueError(f"starting iterates of shapes {z0.shape}, {eta0.shape}, expected "
+                                 f"({B}, {self.P}), ({B}, {self.D})")
+        rows = int(max_iters) + 1
+        err = np.zeros((max(B, 1), max(rows, 1), 3))
+        derr = np.zeros((max(B, 1), max(rows, 1), 3))
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        iters = np.zeros(max(B, 1), dtype=np.int32)
+        self._check(self._lib.raocp_cp_batch_run(
+            self._h, B, _ptr(x0), None if z0 is None else _ptr(z0), None if eta0 is None else _ptr(eta0),
+            int(max_iters), float(tol), float(alpha), _ptr(status), _ptr(iters), _ptr(err), _ptr(derr)))
+        self._batch_B = B
+        return (status.astype(np.int64), [err[b, :iters[b]].copy() for b in range(B)],
+                [derr[b, :iters[b]].copy() for b in range(B)])
+
+    def cp_batch_get(self, b):
+        """(z, eta) of instance b of the last batch, in the reference's flat order."""
+        z, e = np.empty(self.P), np.empty(self.D)
+        self._check(self._lib.raocp_cp_batch_get(self._h, int(b), _ptr(z), _ptr(e)))
+        return z, e
+
+    def cp_batch_first_inputs(self):
+        """(B, nu): the root's input of every instance's final primal."""
+        B = getattr(self, "_batch_B", 0)
+        out = np.zeros((max(B, 1), self._packed.nu))
+        self._check(self._lib.raocp_cp_batch_first_inputs(self._h, _ptr(out)))
+        return out[:B]
 
     def cp_prepare(self, iters, x0=None, alpha=0.0):
         """Capture the CP graphs an `iters`-iteration cp_bench launches and, given x0, reset

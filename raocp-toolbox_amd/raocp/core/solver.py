@@ -20,7 +20,20 @@ import raocp.core.cache as cache
 import raocp.core.operators as ops
 import raocp.core.raocp_spec as spec
 
-__all__ = ["Solver"]
+__all__ = ["Solver", "normalise_initial_states"]
+
+
+def normalise_initial_states(initial_states, nx):
+    """The (B, nx) float64 array of a batch's initial states: accepts (B, nx), (B, nx, 1) and,
+    for one instance, a 1-D array of nx entries; anything else raises ValueError."""
+    a = np.asarray(initial_states, dtype=np.float64)
+    if a.ndim == 1 and a.size == nx:
+        a = a.reshape(1, nx)
+    elif a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim != 2 or a.shape[1] != nx or a.shape[0] < 1:
+        raise ValueError(f"initial_states of shape {np.shape(initial_states)}: expected (B, {nx}) or (B, {nx}, 1)")
+    return np.ascontiguousarray(a)
 
 
 class Solver:
@@ -35,6 +48,9 @@ class Solver:
         self.__delta_error = [np.zeros(1)] * 3
         self.__error_cache = None
         self.__delta_error_cache = None
+        self.__batch_size = 0
+        self.batch_error_cache = []
+        self.batch_delta_error_cache = []
 
     @property
     def cache(self):
@@ -118,6 +134,52 @@ class Solver:
         self.__delta_error_cache = derr if derr.shape[0] > 1 else derr[0]
         self.__cache.update_cache()
         return status
+
+    # ----- batched solves (extension): many initial states, one launch
+    def chock_batch(self, initial_states, max_iters=10, tol=1e-5, step_size=None, warm=False):
+        """Chambolle-Pock for B initial states of the same problem at once (one workgroup per
+        instance on the device). Returns an int array of chock's codes (0 converged, 1 not).
+        warm=True continues every instance from the iterate the previous chock_batch left (the
+        batch size must be the same). Results: batch_error_cache[b], batch_delta_error_cache[b],
+        batch_primal_flat(b), batch_dual_flat(b), batch_first_inputs(). If a NaN reached a box
+        projection in some instances, the results are stored and ValueError names them."""
+        nx = self.__raocp.state_dynamics_at_node(1).shape[1]
+        x0 = normalise_initial_states(initial_states, nx)
+        B = x0.shape[0]
+        native = self.__cache.native
+        z0 = e0 = None
+        if warm:
+            if B != self.__batch_size:
+                raise ValueError(f"warm chock_batch of {B} instances after a batch of {self.__batch_size}")
+            pairs = [native.cp_batch_get(b) for b in range(B)]
+            z0 = np.array([p[0] for p in pairs])
+            e0 = np.array([p[1] for p in pairs])
+        if step_size is None:
+            self.compute_step_size()
+        else:
+            self.__parameter_1 = self.__parameter_2 = float(step_size)
+        print("timer started")
+        tick = time.perf_counter()
+        status, errs, derrs = native.cp_batch_run(x0, int(max_iters), float(tol), self.__parameter_1, z0, e0)
+        tock = time.perf_counter()
+        print(f"timer stopped in {tock - tick:0.4f} seconds")
+        self.__batch_size = B
+        # the shape rules of error_cache: a single row is 1-D (solver.py:148-153)
+        self.batch_error_cache = [e if e.shape[0] > 1 else e[0] for e in errs]
+        self.batch_delta_error_cache = [e if e.shape[0] > 1 else e[0] for e in derrs]
+        bad = [int(b) for b in np.flatnonzero(status == 2)]
+        if bad:
+            raise ValueError(f"Rectangle constraint - 'nan' value cannot be constrained (instances {bad})")
+        return status
+
+    def batch_primal_flat(self, b):
+        return self.__cache.native.cp_batch_get(b)[0]
+
+    def batch_dual_flat(self, b):
+        return self.__cache.native.cp_batch_get(b)[1]
+
+    def batch_first_inputs(self):
+        return self.__cache.native.cp_batch_first_inputs()
 
     # ----- outputs (solver.py:173-253)
     @property
