@@ -134,7 +134,8 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * (k_drc; "" when the loop runs 9 and 10 as separate launches)), as rocprofv3 reports it;
  * op 12: the forms of the k_cp5 launches ("leaf_pf=. fams=. fam_pf=.", "" when k_cp5 does not
  * run); op 13: the batched CP kernel of raocp_cp_batch_run ("" when the batch runs as
- * sequential solves); written NUL-terminated to buf. */
+ * sequential solves); op 14: the step kernel of raocp_cp_batch_mpc ("" when that loop runs on
+ * the host); written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
 /* prox of f on the current primal (Cache.proximal_of_f, cache.py:248-257) and its steps */
@@ -197,6 +198,34 @@ int raocp_cp_batch_run(raocp_ctx* ctx, int B, const double* x0 /*[B][nx]*/,
 int raocp_cp_batch_get(raocp_ctx* ctx, int b, double* z /*[P]*/, double* eta /*[D]*/);
 /* The root's input u_0 of every instance's final primal (what an MPC loop applies). */
 int raocp_cp_batch_first_inputs(raocp_ctx* ctx, double* u0 /*[B][nu]*/);
+
+/* Closed-loop MPC simulation of a batch, resident on the device: T steps of B instances. Step t
+ * solves every instance from its current state (raocp_cp_batch_run's solve, with its own
+ * stopping test), applies the root's input u_0 of the final primal and moves the plant along
+ * the realised scenario j = scen[b][t], an index into the root's children (node
+ * i = ch_start[0] + j): x+ = A_i x + B_i u_0 with the dynamics the context was created with,
+ * realised stage cost |sqrtQ_i x|^2 + |sqrtR_i u_0|^2. The next solve starts from x+ and, with
+ * warm != 0, from this step's final iterate (warm = 0: from zero). One kernel launch per step
+ * (k_mpc_step, raocp_cpb.hip) records the step and restarts the instances inside their slabs;
+ * besides the done poll of the k_cpb launches nothing crosses the host boundary inside the
+ * loop. A context k_cpb does not cover (see raocp_cp_batch_run) runs the same loop on the
+ * host over sequential solves, with the same outputs. Outputs:
+ *   X[b][t]       the state step t was solved from (X[b][0] = x0[b]), X[b][T] the last x+
+ *   U[b][t]       the input applied, cost[b][t] the realised stage cost
+ *   status[b][t]  0 / 1 / 2 and iters[b][t] as raocp_cp_batch_run, err[b][t][0..2] the last row
+ *                 of that solve's error cache
+ * An instance whose solve let a NaN reach a box projection is frozen: that step records status 2
+ * and its iterations, every later step status 2 and 0 iterations (err NaN); U, cost and the
+ * following X are NaN from that step on; the other instances are not affected.
+ * Afterwards raocp_cp_batch_get / raocp_cp_batch_first_inputs describe every instance's last
+ * solve. The context's own iterate and initial state are left as they were. Errors:
+ * RAOCP_ERR_ARG for a NULL pointer, B outside 1 .. 4096, T < 1, max_iters < 0 or a scen entry
+ * outside [0, nch[0]) (checked before anything is launched); RAOCP_ERR_STATE on a sharded
+ * context. kernel_info op 14 names the step kernel ("" when the loop runs on the host). */
+int raocp_cp_batch_mpc(raocp_ctx* ctx, int B, int T, const double* x0 /*[B][nx]*/, const int* scen /*[B][T]*/,
+                       int max_iters, double tol, double alpha, int warm,
+                       double* X /*[B][T+1][nx]*/, double* U /*[B][T][nu]*/, double* cost /*[B][T]*/,
+                       int* status /*[B][T]*/, int* iters /*[B][T]*/, double* err /*[B][T][3]*/);
 
 /* Benchmark helpers (bench.py): raocp_cp_bench runs exactly `iters` CP iterations
  * (tol = 0) from (x0 at node 0, zeros) / 0 on the device, graph-replayed (whole

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <random>
 #include <string>
@@ -233,6 +234,13 @@ struct raocp_ctx {
         std::vector<int> fk;         // final_k per instance
         std::vector<double> hz, he, hu0;  // the sequential solves' final iterates and first inputs
     } bt;
+    // closed-loop simulation of a batch (raocp_cp_batch_mpc): the plant tables of the root's
+    // children (host copies from create; A | B uploaded at the first simulation) and the
+    // device block of the per-step records, reused while it is large enough
+    std::vector<double> h_mpc_ab, h_mpc_w;
+    const double* d_mpc_ab = nullptr;
+    void* mpc_buf = nullptr;
+    size_t mpc_cap = 0;
     std::vector<void*> allocs;
 
     template <class T>
@@ -1468,6 +1476,11 @@ void batch_free(raocp_ctx* c) {
     bt.cap_B = 0;
     bt.hist_rows = 0;
 }
+void mpc_free(raocp_ctx* c) {
+    if (c->mpc_buf) (void)hipFree(c->mpc_buf);
+    c->mpc_buf = nullptr;
+    c->mpc_cap = 0;
+}
 // the kernel the default selection launches for op (raocp_op_bench numbering: 0 L, 1 L^T,
 // 2 dual CP kernel, 6 primal CP kernel, 9 the dynamics projection), as rocprofv3 names it
 std::string kernel_name(const raocp_ctx* c, int op) {
@@ -1535,6 +1548,8 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
         case 13:  // the batched CP kernel, when raocp_cp_batch_run launches it ("" otherwise)
             return cpb_on(c) ? raocp::cpb_name(raocp::cpb_tab_bytes(c->dev) > 0) : "";
+        case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
+            return cpb_on(c) ? raocp::mpc_step_name() : "";
         case 10:
             if (c->cp6 && c->sh_S == 0) return raocp::cp6_name();
             if (c->cp5) return std::string(raocp::cp5_name(c->f32, c->nx)) + (c->sh_S > 0 ? " (+ fams x1 after X1)" : "");
@@ -2095,6 +2110,26 @@ int raocp_ctx_create(const raocp_tree_desc* t, const raocp_problem_desc* pr, int
                 return bail(fail(RAOCP_ERR_ARG, "dynamics index out of range"));
         for (int i = 0; i < m; ++i)
             if (pr->i_k[i] < 0 || pr->i_k[i] >= nk) return bail(fail(RAOCP_ERR_ARG, "class index out of range"));
+        // the plant of a closed-loop simulation (raocp_cp_batch_mpc): per child of the root the
+        // doubles of A_i | B_i, and of sqrt Q_i | sqrt R_i for the realised stage cost (row-major)
+        c->h_mpc_ab.clear();
+        c->h_mpc_w.clear();
+        for (int q = 0; q < t->nch[0]; ++q) {
+            const int i = t->ch_start[0] + q;
+            if (pr->i_sq[i] < 0 || pr->i_sq[i] >= pr->n_sq || pr->i_sr[i] < 0 || pr->i_sr[i] >= pr->n_sr) {
+                c->h_mpc_ab.clear();
+                c->h_mpc_w.clear();
+                break;
+            }
+            const double* a = pr->A + (size_t)pr->i_a[i] * nx * nx;
+            const double* b = pr->B + (size_t)pr->i_b[i] * nx * nu;
+            const double* sq = pr->sqrt_q + (size_t)pr->i_sq[i] * nx * nx;
+            const double* sr = pr->sqrt_r + (size_t)pr->i_sr[i] * nu * nu;
+            c->h_mpc_ab.insert(c->h_mpc_ab.end(), a, a + (size_t)nx * nx);
+            c->h_mpc_ab.insert(c->h_mpc_ab.end(), b, b + (size_t)nx * nu);
+            c->h_mpc_w.insert(c->h_mpc_w.end(), sq, sq + (size_t)nx * nx);
+            c->h_mpc_w.insert(c->h_mpc_w.end(), sr, sr + (size_t)nu * nu);
+        }
         auto A = [&](int t, int r, int k) { return pr->A[((size_t)t * nx + r) * nx + k]; };
         auto Bm = [&](int t, int r, int k) { return pr->B[((size_t)t * nx + r) * nu + k]; };
         auto K = [&](int c_, int r, int k) { return pr->K[((size_t)c_ * nu + r) * nx + k]; };
@@ -2990,6 +3025,7 @@ void raocp_ctx_destroy(raocp_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (void* p : c->allocs) (void)hipFree(p);
     batch_free(c);
+    mpc_free(c);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3077,7 +3113,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }
@@ -3518,6 +3554,237 @@ int batch_run_seq(raocp_ctx* c, int B, const double* x0, const double* z0, const
     return RAOCP_OK;
 }
 
+// ---- closed-loop simulation of a batch (raocp_cp_batch_mpc)
+
+// the per-step records on the device: one block, every array on a 256-B boundary
+struct MpcBufs {
+    int* scen;
+    int* frz;
+    double* X;
+    double* U;
+    double* cost;
+    int* status;
+    int* iters;
+    double* err;
+};
+
+int mpc_ensure(raocp_ctx* c, int B, int T, MpcBufs* mb) {
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) / 256 * 256;
+        return o;
+    };
+    const size_t BT = (size_t)B * T;
+    const size_t o_scen = take(BT * sizeof(int)), o_frz = take((size_t)B * sizeof(int));
+    const size_t o_X = take((size_t)B * (T + 1) * c->nx * sizeof(double)), o_U = take(BT * c->nu * sizeof(double));
+    const size_t o_cost = take(BT * sizeof(double)), o_status = take(BT * sizeof(int)), o_iters = take(BT * sizeof(int));
+    const size_t o_err = take(BT * 3 * sizeof(double));
+    if (at > c->mpc_cap) {
+        mpc_free(c);
+        HIPCHK(hipMalloc(&c->mpc_buf, at));
+        c->mpc_cap = at;
+    }
+    char* base = (char*)c->mpc_buf;
+    mb->scen = (int*)(base + o_scen);
+    mb->frz = (int*)(base + o_frz);
+    mb->X = (double*)(base + o_X);
+    mb->U = (double*)(base + o_U);
+    mb->cost = (double*)(base + o_cost);
+    mb->status = (int*)(base + o_status);
+    mb->iters = (int*)(base + o_iters);
+    mb->err = (double*)(base + o_err);
+    return RAOCP_OK;
+}
+
+// final_k of every instance's last solve: the last step with iterations (a frozen instance's
+// slab keeps the solve that froze it)
+void mpc_final_k(std::vector<int>& fk, int B, int T, const int* iters) {
+    fk.assign(B, 0);
+    for (int b = 0; b < B; ++b)
+        for (int t = T - 1; t >= 0; --t)
+            if (iters[(size_t)b * T + t] > 0) {
+                fk[b] = iters[(size_t)b * T + t] - 1;
+                break;
+            }
+}
+
+// the loop on the device: per step the chunked k_cpb launches with their done poll, then one
+// k_mpc_step launch; nothing else crosses the host boundary inside the T loop
+int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
+                     double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+    auto& bt = c->bt;
+    const size_t rows = (size_t)max_iters + 1, BT = (size_t)B * T;
+    int rc;
+    if (c->h_mpc_ab.empty()) return fail(RAOCP_ERR_STATE, "no plant tables for the root's children");
+    if (!c->d_mpc_ab && (rc = c->upload(&c->d_mpc_ab, c->h_mpc_ab.data(), c->h_mpc_ab.size()))) return rc;
+    if ((rc = batch_ensure(c, B, rows))) return rc;
+    MpcBufs mb{};
+    if ((rc = mpc_ensure(c, B, T, &mb))) return rc;
+    const raocp::CpbSlab& L = bt.lay;
+    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(bt.done, 0, (size_t)B * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(bt.u0, 0, (size_t)B * c->nu * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(mb.frz, 0xff, (size_t)B * sizeof(int), c->stream));  // -1: running
+    if ((rc = batch_scatter(c, L.z[0] + c->dev.X0, x0, (size_t)c->nx, B))) return rc;
+    if ((rc = batch_scatter(c, L.x0, x0, (size_t)c->nx, B))) return rc;
+    HIPCHK(hipMemcpyAsync(mb.scen, scen, BT * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    Ctl h{};
+    h.alpha = alpha;
+    h.final_k = -1;
+    h.max_iters = max_iters;
+    h.tol = tol;
+    const std::vector<Ctl> hc((size_t)B, h);
+    HIPCHK(hipMemcpyAsync(bt.ctl, hc.data(), hc.size() * sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    raocp::CpbArg a{};
+    a.slab = bt.slab;
+    a.lay = L;
+    a.ctl = bt.ctl;
+    a.done = bt.done;
+    a.hist = bt.hist;
+    a.hist_rows = (long)rows;
+    a.u0 = bt.u0;
+    a.B = B;
+    a.chunk = batch_chunk();
+    a.lds_tabs = raocp::cpb_tab_bytes(c->dev) > 0 ? 1 : 0;
+    raocp::MpcArg m{};
+    m.ab = c->d_mpc_ab;
+    m.scen = mb.scen;
+    m.frz = mb.frz;
+    m.X = mb.X;
+    m.U = mb.U;
+    m.cost = mb.cost;
+    m.status = mb.status;
+    m.iters = mb.iters;
+    m.err = mb.err;
+    m.T = T;
+    m.warm = warm ? 1 : 0;
+    std::vector<int> hd((size_t)B, 0);
+    const long launches = (long)(rows + a.chunk - 1) / a.chunk + 1;  // every instance ends within rows iterations
+    for (int t = 0; t < T; ++t) {
+        bool all = false;
+        for (long l = 0; l < launches && !all; ++l) {
+            HIPCHK(raocp::cpb_launch(c->dev, a, c->stream));
+            HIPCHK(hipMemcpyAsync(hd.data(), bt.done, hd.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            all = std::all_of(hd.begin(), hd.end(), [](int v) { return v != 0; });
+        }
+        if (!all) return fail(RAOCP_ERR_STATE, "batched CP kernel: an instance did not finish");
+        m.t = t;
+        m.last = t == T - 1 ? 1 : 0;
+        HIPCHK(raocp::mpc_step_launch(c->dev, a, m, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(X, mb.X, (size_t)B * (T + 1) * c->nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(U, mb.U, BT * c->nu * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cost, mb.cost, BT * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status, mb.status, BT * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(iters, mb.iters, BT * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(err, mb.err, BT * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    mpc_final_k(bt.fk, B, T, iters);
+    bt.B = B;
+    bt.kernel = true;
+    return RAOCP_OK;
+}
+
+// the same loop on the host for a context k_cpb does not cover: per step the running instances'
+// solves through batch_run_seq, the plant step and the stage cost in host arithmetic
+int batch_mpc_seq(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
+                  double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+    auto& bt = c->bt;
+    const int nx = c->nx, nu = c->nu;
+    const size_t P = (size_t)c->P, D = (size_t)c->D, rows = (size_t)max_iters + 1;
+    if (c->h_mpc_ab.empty()) return fail(RAOCP_ERR_STATE, "no plant tables for the root's children");
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> xc(x0, x0 + (size_t)B * nx), Z((size_t)B * P, 0.0), E((size_t)B * D, 0.0), U0((size_t)B * nu, 0.0);
+    std::vector<int> frz(B, -1), act, st(B), itv(B);
+    std::vector<double> ax, az, ae, eh((size_t)B * rows * 3), dh((size_t)B * rows * 3);
+    for (int b = 0; b < B; ++b) std::copy(x0 + (size_t)b * nx, x0 + (size_t)(b + 1) * nx, X + (size_t)b * (T + 1) * nx);
+    auto blank = [&](int b, int t) {
+        const size_t bt_ = (size_t)b * T + t;
+        for (int r = 0; r < nx; ++r) X[((size_t)b * (T + 1) + t + 1) * nx + r] = qnan;
+        for (int r = 0; r < nu; ++r) U[bt_ * nu + r] = qnan;
+        cost[bt_] = qnan;
+        status[bt_] = 2;
+    };
+    for (int t = 0; t < T; ++t) {
+        act.clear();
+        for (int b = 0; b < B; ++b) {
+            if (frz[b] < 0) {
+                act.push_back(b);
+                continue;
+            }
+            blank(b, t);
+            iters[(size_t)b * T + t] = 0;
+            for (int q = 0; q < 3; ++q) err[((size_t)b * T + t) * 3 + q] = qnan;
+        }
+        if (act.empty()) continue;
+        const int nA = (int)act.size();
+        const bool cont = warm && t > 0;
+        ax.resize((size_t)nA * nx);
+        for (int q = 0; q < nA; ++q) std::copy(xc.begin() + (size_t)act[q] * nx, xc.begin() + (size_t)(act[q] + 1) * nx, ax.begin() + (size_t)q * nx);
+        if (cont) {
+            az.resize((size_t)nA * P);
+            ae.resize((size_t)nA * D);
+            for (int q = 0; q < nA; ++q) {
+                std::copy(Z.begin() + act[q] * P, Z.begin() + (act[q] + 1) * P, az.begin() + q * P);
+                std::copy(E.begin() + act[q] * D, E.begin() + (act[q] + 1) * D, ae.begin() + q * D);
+            }
+        }
+        const int rc = batch_run_seq(c, nA, ax.data(), cont ? az.data() : nullptr, cont ? ae.data() : nullptr, max_iters, tol,
+                                     alpha, st.data(), itv.data(), eh.data(), dh.data());
+        bt.B = 0;
+        if (rc) return rc;
+        for (int q = 0; q < nA; ++q) {
+            const int b = act[q];
+            const size_t bt_ = (size_t)b * T + t;
+            std::copy(bt.hz.begin() + q * P, bt.hz.begin() + (q + 1) * P, Z.begin() + b * P);
+            std::copy(bt.he.begin() + q * D, bt.he.begin() + (q + 1) * D, E.begin() + b * D);
+            std::copy(bt.hu0.begin() + (size_t)q * nu, bt.hu0.begin() + (size_t)(q + 1) * nu, U0.begin() + (size_t)b * nu);
+            iters[bt_] = itv[q];
+            for (int r = 0; r < 3; ++r) err[bt_ * 3 + r] = itv[q] > 0 ? eh[((size_t)q * rows + itv[q] - 1) * 3 + r] : qnan;
+            if (st[q] == 2) {
+                frz[b] = t;
+                blank(b, t);
+                continue;
+            }
+            status[bt_] = st[q];
+            const int j = scen[bt_];
+            const double* A = c->h_mpc_ab.data() + (size_t)j * (nx + nu) * nx;
+            const double* Bm = A + (size_t)nx * nx;
+            const double* SQ = c->h_mpc_w.data() + (size_t)j * ((size_t)nx * nx + (size_t)nu * nu);
+            const double* SR = SQ + (size_t)nx * nx;
+            const double* x = xc.data() + (size_t)b * nx;
+            const double* u = U0.data() + (size_t)b * nu;
+            double* xp = X + ((size_t)b * (T + 1) + t + 1) * nx;
+            double l = 0.0;
+            for (int r = 0; r < nx; ++r) {
+                double s = 0.0, w = 0.0;
+                for (int k = 0; k < nx; ++k) s = std::fma(A[(size_t)r * nx + k], x[k], s);
+                for (int k = 0; k < nu; ++k) s = std::fma(Bm[(size_t)r * nu + k], u[k], s);
+                for (int k = 0; k < nx; ++k) w = std::fma(SQ[(size_t)r * nx + k], x[k], w);
+                xp[r] = s;
+                l += w * w;
+            }
+            for (int r = 0; r < nu; ++r) {
+                double w = 0.0;
+                for (int k = 0; k < nu; ++k) w = std::fma(SR[(size_t)r * nu + k], u[k], w);
+                l += w * w;
+                U[bt_ * nu + r] = u[r];
+            }
+            cost[bt_] = l;
+            std::copy(xp, xp + nx, xc.begin() + (size_t)b * nx);
+        }
+    }
+    bt.hz = Z;
+    bt.he = E;
+    bt.hu0 = U0;
+    mpc_final_k(bt.fk, B, T, iters);
+    bt.B = B;
+    bt.kernel = false;
+    return RAOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3564,6 +3831,24 @@ int raocp_cp_batch_first_inputs(raocp_ctx* c, double* u0) {
     }
     HIPCHK(hipMemcpy(u0, bt.u0, (size_t)bt.B * c->nu * sizeof(double), hipMemcpyDeviceToHost));
     return RAOCP_OK;
+}
+
+int raocp_cp_batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
+                       double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+    DevGuard dg_(c);
+    if (!c || !x0 || !scen || !X || !U || !cost || !status || !iters || !err) return fail(RAOCP_ERR_ARG, "null argument");
+    if (B < 1 || B > 4096) return fail(RAOCP_ERR_ARG, "batch size must be in 1 .. 4096");
+    if (T < 1) return fail(RAOCP_ERR_ARG, "the number of steps must be >= 1");
+    if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
+    if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "batched solves are not available on a sharded context");
+    const int nc = c->h_nch.empty() ? 0 : c->h_nch[0];
+    for (size_t q = 0; q < (size_t)B * T; ++q)
+        if (scen[q] < 0 || scen[q] >= nc)
+            return fail(RAOCP_ERR_ARG, "scenario entry " + std::to_string(scen[q]) + " is not a child of the root (0 .. " +
+                                           std::to_string(nc - 1) + ")");
+    c->bt.B = 0;
+    if (cpb_on(c)) return batch_mpc_kernel(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
+    return batch_mpc_seq(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
 }
 
 int raocp_cp_prepare(raocp_ctx* c, const double* x0, int iters, double alpha) {

@@ -39,10 +39,30 @@ struct CpbArg {
     int lds_tabs;      // the L weights and the box tables are staged in LDS
 };
 
+// k_mpc_step: the end of one closed-loop MPC step of a batch and the start of the next, inside
+// the slabs (after every instance of the batch is done with step t)
+struct MpcArg {
+    const double* ab;    // [nch[0]] {A_i (nx x nx) | B_i (nx x nu)} row-major, i = ch_start[0] + j
+    const int* scen;     // [B][T] realised root child j of instance b at step t
+    int* frz;            // [B] the step at which the instance froze (NaN in a box), -1: running
+    double* X;           // [B][T + 1][nx]
+    double* U;           // [B][T][nu]
+    double* cost;        // [B][T]
+    int* status;         // [B][T]
+    int* iters;          // [B][T]
+    double* err;         // [B][T][3]
+    int T;
+    int t;               // the step that ends
+    int warm;            // the next solve starts from this step's final iterate (else from zero)
+    int last;            // t == T - 1: record only, the slab keeps the last solve
+};
+
 CpbSlab cpb_layout(const Dev& p);
 // bytes of LDS the staged tables take, 0 when they exceed kCpbLdsTabs (then read from HBM)
 size_t cpb_tab_bytes(const Dev& p);
 hipError_t cpb_launch(const Dev& p, const CpbArg& a, hipStream_t stream);
 const char* cpb_name(bool lds_tabs);
+hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, hipStream_t stream);
+const char* mpc_step_name();
 
 }  // namespace raocp

@@ -597,6 +597,126 @@ __global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
     }
 }
 
+// ---- k_mpc_step: the end of step t of a closed-loop simulation and the start of step t + 1,
+// one workgroup per instance, launched after every instance of the batch is done with step t.
+//   1. x = the slab's x0, u = the root's input of the final primal Z[(final_k + 1) % 3]; with
+//      i = ch_start[0] + scen[b][t]: x+ = A_i x + B_i u (one lane per row, k ascending, fma) and
+//      l = |SQ_i x|^2 + |SR_i u|^2 (one lane per row of SQ_i / SR_i, lane 0 adds the squares in
+//      row order); X[b][t + 1], U[b][t], cost[b][t], status, iters and the xi maxima of the last
+//      history row are recorded
+//   2. unless this was the last step: the final iterate moves to Z[0] / E[0] (warm; 16-B
+//      copies, skipped when it is there already), the rest of the slab is cleared as the
+//      host's memset of a fresh batch leaves it (16-B stores), x+ goes to node 0's state of
+//      Z[0] and to the slab's x0, and the instance's Ctl and done word are reset.
+// An instance whose solve raised the NaN flag is frozen: its slab, Ctl and done word stay, this
+// step and every later one record status 2 (later ones: 0 iterations) and NaN for x+, u, l.
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) d2 glbd2;
+
+__global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg m) {
+    __shared__ double s_x[kCpbMaxNx], s_u[kCpbMaxNu], s_xp[kCpbMaxNx], s_sq[kCpbMaxNx + kCpbMaxNu];
+    const int b = blockIdx.x;
+    if (b >= a.B) return;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int nx = p.nx, nu = p.nu, T = m.T, t = m.t;
+    Ctl* ctl = a.ctl + b;
+    double* slab = a.slab + (size_t)b * a.lay.stride;
+    glbd* Xo = (glbd*)(m.X + ((size_t)b * (T + 1) + t) * nx);
+    glbd* Uo = (glbd*)(m.U + ((size_t)b * T + t) * nu);
+    const size_t bt = (size_t)b * T + t;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    // uniform over the workgroup: nobody writes these words before the barrier below
+    const int fk = ctl->final_k, flags = ctl->flags, max_iters = ctl->max_iters;
+    const int frz = m.frz[b];
+    cgd x = (cgd)(slab + a.lay.x0);
+    if (t == 0 && tid < nx) Xo[tid] = x[tid];
+    if (frz >= 0 || (flags & 1)) {
+        if (tid < nx) Xo[nx + tid] = qnan;
+        if (tid < nu) Uo[tid] = qnan;
+        if (tid < 3) m.err[bt * 3 + tid] = frz >= 0 ? qnan : a.hist[((size_t)b * a.hist_rows + fk) * 6 + tid];
+        if (tid == 0) {
+            m.cost[bt] = qnan;
+            m.status[bt] = 2;
+            m.iters[bt] = frz >= 0 ? 0 : fk + 1;
+        }
+        __syncthreads();  // every lane has read frz[b]
+        if (tid == 0 && frz < 0) m.frz[b] = t;
+        return;
+    }
+    const int zs = (fk + 1) % 3, es = (fk + 1) % 2;
+    cgd zf = (cgd)(slab + a.lay.z[zs]);
+    if (tid < nx) s_x[tid] = x[tid];
+    if (tid < nu) s_u[tid] = zf[p.U0 + tid];
+    __syncthreads();
+    const int j = m.scen[bt];
+    const int i = ((glbi*)p.ch_start)[0] + j;
+    const Rec cr = ((glbrec*)p.crec)[i];
+    if (tid < nx) {
+        cgd Ar = (cgd)m.ab + ((size_t)j * (nx + nu) + tid) * nx;
+        cgd Br = (cgd)m.ab + ((size_t)j * (nx + nu) + nx) * nx + (size_t)tid * nu;
+        double s = 0.0;
+        for (int k = 0; k < nx; ++k) s = fma(Ar[k], s_x[k], s);
+        for (int k = 0; k < nu; ++k) s = fma(Br[k], s_u[k], s);
+        s_xp[tid] = s;
+        Xo[nx + tid] = s;
+    } else if (tid >= 64 && tid < 64 + nx + nu) {
+        // the column-major L weights: M[k * rows + r] = M_rk
+        const int r = tid - 64;
+        const bool isx = r < nx;
+        const int rr = isx ? r : r - nx, len = isx ? nx : nu;
+        cgd M = isx ? (cgd)p.SQ + (size_t)cr.y * nx * nx + rr : (cgd)p.SR + (size_t)cr.z * nu * nu + rr;
+        const double* v = isx ? s_x : s_u;
+        double s = 0.0;
+        for (int k = 0; k < len; ++k) s = fma(M[k * len], v[k], s);
+        s_sq[r] = s * s;
+    }
+    if (tid < nu) Uo[tid] = s_u[tid];
+    if (tid < 3) m.err[bt * 3 + tid] = a.hist[((size_t)b * a.hist_rows + fk) * 6 + tid];
+    __syncthreads();
+    if (tid == 0) {
+        double l = 0.0;
+        for (int r = 0; r < nx + nu; ++r) l += s_sq[r];
+        m.cost[bt] = l;
+        m.status[bt] = fk < max_iters ? 0 : 1;
+        m.iters[bt] = fk + 1;
+    }
+    if (m.last) return;
+    // every array of the slab starts on a 16-B boundary and has an even length in the layout
+    // (cpb_layout: Z[0] at the slab's start, then Z[1], Z[2], E[0], E[1] and the work arrays)
+    const CpbSlab& L = a.lay;
+    glbd2* s2 = (glbd2*)slab;
+    const d2 zero = {0.0, 0.0};
+    const long z1 = L.z[1] / 2, e0 = L.e[0] / 2, e1 = L.e[1] / 2, end = L.stride / 2;
+    if (m.warm) {
+        if (zs != 0) {
+            const long src = L.z[zs] / 2;
+            for (long q = tid; q < z1; q += nthr) s2[q] = s2[src + q];
+        }
+        if (es != 0)
+            for (long q = tid; q < e1 - e0; q += nthr) s2[e0 + q] = s2[e1 + q];
+        __syncthreads();  // the copies have read Z[zs] and E[1] before they are cleared
+        for (long q = z1 + tid; q < e0; q += nthr) s2[q] = zero;
+        for (long q = e1 + tid; q < end; q += nthr) s2[q] = zero;
+    } else {
+        for (long q = tid; q < end; q += nthr) s2[q] = zero;
+    }
+    __syncthreads();  // x+ lands in ranges other lanes have just written
+    if (tid < nx) {
+        const double v = s_xp[tid];
+        ((glbd*)slab)[L.z[0] + p.X0 + tid] = v;
+        ((glbd*)slab)[L.x0 + tid] = v;
+    }
+    if (tid == 0) {
+        _Pragma("unroll") for (int q = 0; q < 6; ++q) ctl->red[q] = 0;
+        ctl->k = 0;
+        ctl->done = 0;
+        ctl->final_k = -1;
+        ctl->flags = 0;
+        ctl->pad = 0;
+        a.done[b] = 0;
+    }
+}
+
 long tab_doubles(const Dev& p) {
     return (long)p.nSQ * p.nx * p.nx + (long)p.nSR * p.nu * p.nu + (long)p.nSP * p.nx * p.nx +
            2L * p.nBnl * (p.nx + p.nu) + 2L * p.nBl * p.nx;
@@ -638,5 +758,12 @@ hipError_t cpb_launch(const Dev& p, const CpbArg& a, hipStream_t stream) {
 }
 
 const char* cpb_name(bool lds_tabs) { return lds_tabs ? "k_cpb<true>" : "k_cpb<false>"; }
+
+hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, hipStream_t stream) {
+    k_mpc_step<<<a.B, kCpbBlock, 0, stream>>>(p, a, m);
+    return hipGetLastError();
+}
+
+const char* mpc_step_name() { return "k_mpc_step"; }
 
 }  // namespace raocp

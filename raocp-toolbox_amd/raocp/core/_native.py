@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "raocp_device_synchronize", "raocp_debug_dyn_stamps",
     "raocp_shard_setup", "raocp_shard_owned", "raocp_comm_unique_id", "raocp_comm_init", "raocp_group_cp_run",
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
-    "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs",
+    "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs", "raocp_cp_batch_mpc",
 ]
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -98,6 +98,8 @@ def load_library():
         "raocp_cp_batch_run": (c_int, [vp, c_int, vp, vp, vp, c_int, c_double, c_double, vp, vp, vp, vp]),
         "raocp_cp_batch_get": (c_int, [vp, c_int, vp, vp]),
         "raocp_cp_batch_first_inputs": (c_int, [vp, vp]),
+        "raocp_cp_batch_mpc": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_double, c_double, c_int,
+                                       vp, vp, vp, vp, vp, vp]),
         "raocp_cp_prepare": (c_int, [vp, vp, c_int, c_double]),
         "raocp_cp_bench": (c_int, [vp, vp, c_int, c_double, ctypes.POINTER(ctypes.c_float)]),
         "raocp_op_bench": (c_int, [vp, c_int, c_int, ctypes.POINTER(ctypes.c_float)]),
@@ -375,6 +377,35 @@ class NativeContext:
         out = np.zeros((max(B, 1), self._packed.nu))
         self._check(self._lib.raocp_cp_batch_first_inputs(self._h, _ptr(out)))
         return out[:B]
+
+    def cp_batch_mpc(self, x0, scen, max_iters, tol, alpha, warm=True):
+        """Closed-loop simulation of a batch on the device: x0 is (B, nx), scen (B, T) integer
+        indices into the root's children. Returns (X (B, T+1, nx), U (B, T, nu), cost (B, T),
+        status (B, T), iters (B, T), err (B, T, 3)); afterwards cp_batch_get / cp_batch_first_inputs
+        describe every instance's last solve."""
+        self._require_l()
+        nx, nu = self._packed.nx, self._packed.nu
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
+        if x0.ndim != 2 or x0.shape[1] != nx:
+            raise ValueError(f"initial states of shape {x0.shape}, expected (B, {nx})")
+        B = x0.shape[0]
+        scen = np.ascontiguousarray(np.asarray(scen, dtype=np.int32))
+        if scen.ndim != 2 or scen.shape[0] != B:
+            raise ValueError(f"scenarios of shape {scen.shape}, expected ({B}, T)")
+        T = scen.shape[1]
+        b1, t1 = max(B, 1), max(T, 1)
+        X = np.zeros((b1, t1 + 1, nx))
+        U = np.zeros((b1, t1, nu))
+        cost = np.zeros((b1, t1))
+        status = np.zeros((b1, t1), dtype=np.int32)
+        iters = np.zeros((b1, t1), dtype=np.int32)
+        err = np.zeros((b1, t1, 3))
+        self._check(self._lib.raocp_cp_batch_mpc(
+            self._h, B, T, _ptr(x0), _ptr(scen) if scen.size else _ptr(np.zeros(1, dtype=np.int32)),
+            int(max_iters), float(tol), float(alpha), int(bool(warm)),
+            _ptr(X), _ptr(U), _ptr(cost), _ptr(status), _ptr(iters), _ptr(err)))
+        self._batch_B = B
+        return X, U, cost, status.astype(np.int64), iters.astype(np.int64), err
 
     def cp_prepare(self, iters, x0=None, alpha=0.0):
         """Capture the CP graphs an `iters`-iteration cp_bench launches and, given x0, reset

@@ -20,7 +20,7 @@ import raocp.core.cache as cache
 import raocp.core.operators as ops
 import raocp.core.raocp_spec as spec
 
-__all__ = ["Solver", "normalise_initial_states"]
+__all__ = ["Solver", "normalise_initial_states", "normalise_scenarios", "sample_scenarios", "BatchSimulation"]
 
 
 def normalise_initial_states(initial_states, nx):
@@ -34,6 +34,43 @@ def normalise_initial_states(initial_states, nx):
     if a.ndim != 2 or a.shape[1] != nx or a.shape[0] < 1:
         raise ValueError(f"initial_states of shape {np.shape(initial_states)}: expected (B, {nx}) or (B, {nx}, 1)")
     return np.ascontiguousarray(a)
+
+
+def normalise_scenarios(scenarios, B, T, n_children):
+    """The (B, T) int32 array of a simulation's realised scenarios (indices into the root's
+    children): a wrong shape, a non-integer dtype or an entry outside [0, n_children) raises
+    ValueError."""
+    a = np.asarray(scenarios)
+    if a.shape != (B, T):
+        raise ValueError(f"scenarios of shape {a.shape}: expected ({B}, {T})")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"scenarios of dtype {a.dtype}: expected integers")
+    if a.size and (a.min() < 0 or a.max() >= n_children):
+        raise ValueError(f"scenario entries must be in [0, {n_children}): found {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def sample_scenarios(probabilities, B, T, seed=None):
+    """(B, T) i.i.d. draws of a root child from the children's conditional probabilities with
+    np.random.default_rng(seed)."""
+    p = np.asarray(probabilities, dtype=np.float64).reshape(-1)
+    rng = np.random.default_rng(seed)
+    return rng.choice(p.size, size=(B, T), p=p / p.sum()).astype(np.int32)
+
+
+class BatchSimulation:
+    """The result of Solver.simulate_batch: states (B, T+1, nx), inputs (B, T, nu),
+    stage_costs (B, T), status (B, T), iterations (B, T), errors (B, T, 3) and the realised
+    scenarios (B, T)."""
+
+    def __init__(self, states, inputs, stage_costs, status, iterations, errors, scenarios):
+        self.states = states
+        self.inputs = inputs
+        self.stage_costs = stage_costs
+        self.status = status
+        self.iterations = iterations
+        self.errors = errors
+        self.scenarios = scenarios
 
 
 class Solver:
@@ -51,6 +88,7 @@ class Solver:
         self.__batch_size = 0
         self.batch_error_cache = []
         self.batch_delta_error_cache = []
+        self.batch_simulation = None
 
     @property
     def cache(self):
@@ -171,6 +209,45 @@ class Solver:
         if bad:
             raise ValueError(f"Rectangle constraint - 'nan' value cannot be constrained (instances {bad})")
         return status
+
+    # ----- closed-loop simulation of a batch (extension), resident on the device
+    def simulate_batch(self, initial_states, num_steps, scenarios=None, seed=None, max_iters=10, tol=1e-5,
+                       step_size=None, warm=True):
+        """Closed-loop MPC over num_steps steps for B initial states at once: every step solves
+        each instance from its current state, applies the root's input and moves the plant along
+        the realised scenario (x+ = A_i x + B_i u_0 for the root's child i); warm=True starts each
+        solve from the previous step's final iterate. `scenarios` is a (B, num_steps) integer
+        array of indices into the root's children; None draws them i.i.d. from the children's
+        conditional probabilities with np.random.default_rng(seed). Returns a BatchSimulation
+        (also kept as `batch_simulation`); afterwards batch_primal_flat(b), batch_dual_flat(b)
+        and batch_first_inputs() describe every instance's last solve. If a NaN reached a box
+        projection in some instances, those are frozen from that step on, the results are
+        stored and ValueError names them."""
+        nx = self.__raocp.state_dynamics_at_node(1).shape[1]
+        x0 = normalise_initial_states(initial_states, nx)
+        B, T = x0.shape[0], int(num_steps)
+        tree = self.__raocp.tree
+        if scenarios is None:
+            scen = sample_scenarios(tree.conditional_probabilities_of_children(0), B, T, seed)
+        else:
+            scen = normalise_scenarios(scenarios, B, T, len(tree.children_of(0)))
+        if step_size is None:
+            self.compute_step_size()
+        else:
+            self.__parameter_1 = self.__parameter_2 = float(step_size)
+        print("timer started")
+        tick = time.perf_counter()
+        X, U, cost, status, iters, err = self.__cache.native.cp_batch_mpc(x0, scen, int(max_iters), float(tol),
+                                                                          self.__parameter_1, warm)
+        tock = time.perf_counter()
+        print(f"timer stopped in {tock - tick:0.4f} seconds")
+        self.__batch_size = B
+        self.batch_simulation = BatchSimulation(X, U, cost, status, iters, err, scen)
+        bad = [int(b) for b in np.flatnonzero((status == 2).any(axis=1))]
+        if bad:
+            step = [int(np.argmax(status[b] == 2)) for b in bad]
+            raise ValueError(f"Rectangle constraint - 'nan' value cannot be constrained (instances {bad} at steps {step})")
+        return self.batch_simulation
 
     def batch_primal_flat(self, b):
         return self.__cache.native.cp_batch_get(b)[0]
