@@ -135,7 +135,11 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * op 12: the forms of the k_cp5 launches ("leaf_pf=. fams=. fam_pf=.", "" when k_cp5 does not
  * run); op 13: the batched CP kernel of raocp_cp_batch_run ("" when the batch runs as
  * sequential solves); op 14: the step kernel of raocp_cp_batch_mpc ("" when that loop runs on
- * the host); written NUL-terminated to buf. */
+ * the host); op 15: the composed maps active in the regular-tree sweep (k_dr / k_drc), as
+ * space-separated "name@tier" terms: "mid_back_root@k" = tier k (between the top and the
+ * deepest) publishes its root's q row from one composed product before its backward levels;
+ * "" when none is (RAOCP_DR_XFER=0, a plan with no such tier or with a tier of more than 4
+ * levels, another sweep); written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
 /* prox of f on the current primal (Cache.proximal_of_f, cache.py:248-257) and its steps */

@@ -5,6 +5,7 @@
 
 #include "raocp_kernels.hip"
 #include "raocp_dynr.h"
+#include "raocp_drxfer.h"
 #include "raocp_cp4.h"
 #include "raocp_cp5.h"
 #include "raocp_cpb.h"
@@ -950,8 +951,35 @@ int dr_setup(raocp_ctx* c, const std::vector<double>& WT, int SKP, const std::ve
     // timing-only bits (no DMA / arithmetic / write-out) exist in diagnostic builds only
     // (the timing bits pass where the sweep's unit is a diagnostic build: VAR_UNIT=dynr variants)
     if (const char* e = getenv("RAOCP_DR_FAULT")) p.fault = atoi(e) & ((raocp::kDiag || raocp::dr_diag_build()) ? ~0 : 1);
+    // composed maps (raocp_drxfer.h), from the arrays the stage tables above come from: a tier
+    // between the top and the deepest, of binary subtrees with 4 levels at 20 / 8, publishes its
+    // root's q row from one composed product before its backward levels. One map per such tier
+    // (one class per stage and one pair per slot: every subtree of a tier shares it), uploaded
+    // once. RAOCP_DR_XFER=0 keeps every row level by level.
+    bool xfer = true;
+    if (const char* e = getenv("RAOCP_DR_XFER")) xfer = atoi(e) != 0;
+    std::vector<double> xbq;
+    int lmax = 0;
+    for (int k = 0; k < T; ++k) lmax = std::max(lmax, p.t[k].L);
+    // (plans of at most 4 levels per tier: the kernel compiled for them holds the composed step)
+    if (xfer && C == 2 && nx == raocp::kXbNx && nu == raocp::kXbNu && T > 2 && lmax <= 4) {
+        xbq.assign((size_t)(T - 2) * raocp::kDrXbN, 0.0);
+        for (int k = 1; k + 1 < T; ++k) {
+            if (p.t[k].L != raocp::kXbL) continue;
+            raocp::XbStages xs;
+            xs.sphi = SKP;
+            xs.srg = SNU;
+            for (int l = 0; l < raocp::kXbL; ++l) {
+                const raocp::Dy3Stage& st = c->reg_st[p.t[k].s0 + l];
+                for (int q = 0; q < 2; ++q) xs.phi[l][q] = &WT[((size_t)st.pair[q] * R + nu) * SKP];
+                xs.rgq[l] = &RG[((size_t)st.cls * R + nu) * SNU];
+            }
+            raocp::xb_pack(raocp::xb_compose(xs), &xbq[(size_t)(k - 1) * raocp::kDrXbN]);
+            p.t[k].xf |= raocp::kDrXfMidBack;
+        }
+    }
     int rc;
-    const double *bi = nullptr, *fi = nullptr;
+    const double *bi = nullptr, *fi = nullptr, *xq = nullptr;
     unsigned long long *gq = nullptr, *gx = nullptr;
     unsigned* sy = nullptr;
     c->dr_gran = (size_t)w * 2 * nx;
@@ -961,8 +989,10 @@ int dr_setup(raocp_ctx* c, const std::vector<double>& WT, int SKP, const std::ve
     HIPCHK(hipMemset(sy, 0, 2 * sizeof(unsigned)));
     HIPCHK(hipMemset(gq, 0, c->dr_gran * sizeof(unsigned long long)));
     HIPCHK(hipMemset(gx, 0, c->dr_gran * sizeof(unsigned long long)));
+    if (!xbq.empty() && (rc = c->upload_vec(&xq, xbq))) return rc;
     p.bimg = bi;
     p.fimg = fi;
+    p.xbq = xq;
     p.gq = gq;
     p.gx = gx;
     p.sync = sy;
@@ -1543,6 +1573,13 @@ std::string kernel_name(const raocp_ctx* c, int op) {
         }
         case 11:  // the CP loop's fused launch (dynamics projection + CP iteration), if any
             return c->drc && c->sh_S == 0 ? raocp::drc_name() : "";
+        case 15: {  // the composed maps of the regular-tree sweep that are active ("" when none)
+            std::string s;
+            if (c->dr && c->sh_S == 0)
+                for (int k = 0; k < c->drp.T; ++k)
+                    if (c->drp.t[k].xf & raocp::kDrXfMidBack) s += (s.empty() ? "" : " ") + std::string("mid_back_root@") + std::to_string(k);
+            return s;
+        }
         case 12:  // the forms of the k_cp5 launches, when they run ("" otherwise)
             if (!c->cp5) return "";
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
@@ -3113,7 +3150,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }

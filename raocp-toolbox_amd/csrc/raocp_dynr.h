@@ -19,7 +19,11 @@ struct DrTier {
     int nsub;  // subtrees (C^s0)
     int b0;    // first workgroup of the tier (the deepest tier first, the top last)
     int w0;    // first hand-off slot of the tier (one per subtree; the top's is unused)
+    int xf;    // composed maps of the tier (kDrXf*), 0: every row level by level
 };
+// DrTier::xf bit 0: a tier between the top and the deepest publishes its root's q row from the
+// composed map DrPlan::xbq (raocp_drxfer.h) before its backward levels
+constexpr int kDrXfMidBack = 1;
 
 // kernel argument of k_dr (passed by value)
 struct DrPlan {
@@ -32,6 +36,7 @@ struct DrPlan {
     int X0, U0;               // iterate offsets of x and u
     const double* bimg;       // backward tables, per nonleaf stage (dr_tb_n doubles each)
     const double* fimg;       // forward tables, per nonleaf stage (dr_tf_n doubles each)
+    const double* xbq;        // composed root maps (kDrXbN doubles each): tier k's at (k - 1) kDrXbN
     const double* zpage;      // 16 doubles of zeros (LDS-DMA source of padding)
     const double* x0;         // x0bar
     unsigned long long* gq;   // up hand-offs: per slot the root's q row, 2 nx granules {half, tag}

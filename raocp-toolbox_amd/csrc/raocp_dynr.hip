@@ -18,7 +18,8 @@
 //   1. stages its x and u rows and its backward tables (LDS-DMA, in the order they are used),
 //   2. (above the deepest tier) waits for its C^L child subtrees' q rows,
 //   3. sweeps its levels backward: d_i into its [x | d] rows, q_i over x_i in place,
-//   4. publishes its root's q row (below the top),
+//   4. publishes its root's q row (below the top; a tier between the top and the deepest with
+//      a composed root map publishes it from that map before step 3, see XbRoot below),
 //   5. (below the top) waits for its root's x row from the parent subtree (the top takes x0bar),
 //   6. sweeps its levels forward: children's x rows and u_i into LDS,
 //   7. publishes its boundary x rows to the child subtrees, then writes x and u to the iterate.
@@ -43,6 +44,7 @@
 // and the granules, raocp_capi.hip).
 
 #include "raocp_dynr.h"
+#include "raocp_drxfer.h"
 #define RAOCP_AMAX_BITS
 // sum_h by shuffles here: the row-swap form (raocp_tile.h) spills 4 VGPRs in k_drc and measured
 // 0.25 us per iteration slower (profiles/r06/drc_variants.log)
@@ -302,6 +304,56 @@ __device__ __forceinline__ void fwd_level(const ldsd* tf, const ldsd* xd, ldsd* 
             ul[m * NU + (s - C * NX)] = acc;
         }
     }
+    }
+}
+
+// ---- the composed root map of a tier between the top and the deepest (raocp_drxfer.h; binary
+// subtrees of 4 levels at 20 / 8): the root's q row as one product of the rows the workgroup
+// holds before its backward sweep, so that the parent's wait ends one step after the children's
+// q rows have landed and the four levels run behind the publish. Lane t = 24 r + c < 480 holds
+// entries [30 c, 30 c + 30) of output row r (15 16-B words, loaded before the wait for the
+// children's rows); input e of [x of nodes 1..14 | boundary q | u] sits at XD + 28 + e +
+// 8 min(e / 20, 14) (the x rows carry 8 d entries each; XL and U follow XD). A group of 8 lanes
+// sums by DPP, a row's three group sums go to LDS entries no input and no level before the next
+// barrier touches (d entries of nodes 0..6, then the x0bar row, unused below the top) and the
+// row's two granule lanes add them in a fixed order: no atomics, the same bits every run.
+struct XbRoot {
+    d2v w[kXbPairs];
+};
+__device__ __forceinline__ void xb_load(const double* img, XbRoot& m) {
+    const int t = threadIdx.x < kXbLanes ? threadIdx.x : 0;
+    _Pragma("unroll") for (int p = 0; p < kXbPairs; ++p) m.w[p] = *(const glb2*)(img + 2 * ((size_t)p * kXbLanes + t));
+}
+__device__ __forceinline__ ldsd* xb_part(ldsd* XD, ldsd* X0B, int q) {
+    return q < 56 ? XD + (q >> 3) * (kXbNx + kXbNu) + kXbNx + (q & 7) : X0B + (q - 56);
+}
+__device__ __forceinline__ void xb_apply(const XbRoot& m, ldsd* XD, ldsd* X0B) {
+    constexpr int SXD = kXbNx + kXbNu;
+    static_assert(3 * kXbNx - 56 <= kXbNx, "group sums: 7 d rows and the x0bar row");
+    const int t = threadIdx.x, r = t / kXbChunks, c = t - r * kXbChunks;
+    double acc = 0.0;
+    if (t < kXbLanes) {
+        d2v a = {0.0, 0.0}, b = {0.0, 0.0};
+        _Pragma("unroll") for (int p = 0; p < kXbPairs; ++p) {
+            const int e = kXbPer * c + 2 * p, n = e / kXbNx;
+            const d2v v = ld2(XD + SXD + e + kXbNu * (n < kXbNodes - 1 ? n : kXbNodes - 1));
+            if (p & 1) b += m.w[p] * v;
+            else a += m.w[p] * v;
+        }
+        acc = (a.x + a.y) + (b.x + b.y);
+    }
+    acc += dpp_x<0xB1>(acc);   // lane ^ 1
+    acc += dpp_x<0x4E>(acc);   // lane ^ 2
+    acc += dpp_x<0x141>(acc);  // the other quad of the 8 (row half-mirror)
+    if (t < kXbLanes && (c & 7) == 0) *xb_part(XD, X0B, 3 * r + (c >> 3)) = acc;
+}
+// behind the barrier that follows xb_apply: granule g = (row g / 2, half g % 2) of q_0
+__device__ __forceinline__ void xb_publish(unsigned long long* dst, unsigned tag, ldsd* XD, ldsd* X0B) {
+    const int g = threadIdx.x;
+    if (g < 2 * kXbNx) {
+        const int r = g >> 1;
+        const double q = ((*xb_part(XD, X0B, 3 * r) + *xb_part(XD, X0B, 3 * r + 1)) + *xb_part(XD, X0B, 3 * r + 2)) - XD[r];
+        st_gran(dst + g, (g & 1) ? (unsigned)__double2hiint(q) : (unsigned)__double2loint(q), tag);
     }
 }
 
@@ -1255,6 +1307,13 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
             constexpr int l = L - 1 - ic.value;
             TB::issue(SL + l * SLOT, pl.bimg + (size_t)(s0 + l) * TBN);
         });
+    // the composed root map's share of this lane, in registers across the wait below
+    // (the kernels of plans with at most 4 levels per tier only: UMAX = 1, the 128-VGPR bodies)
+    constexpr bool XBC = C == 2 && L == 4 && UMAX == 1 && NX == kXbNx && NU == kXbNu;
+    const bool xroot = XBC && !top && !deepest && (tt.xf & kDrXfMidBack) != 0;
+    XbRoot xm;
+    if constexpr (XBC)
+        if (xroot) xb_load(pl.xbq + (size_t)(k - 1) * kDrXbN, xm);
     // ---- 2. the child subtrees' q rows
     if (!deepest) {
         const DrTier& ct = pl.t[k + 1];
@@ -1266,6 +1325,14 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
     dma_wait();
     lds_sync();
     stamp(pl, stp);
+    // the root's q row up from the composed map: the levels below then run behind the publish
+    if constexpr (XBC)
+        if (xroot) {
+            xb_apply(xm, XD, X0B);
+            lds_sync();
+            xb_publish(pl.gq + (size_t)(tt.w0 + o) * G, tag, XD, X0B);
+            stamp(pl, stp);
+        }
     // ---- 3. backward sweep; each used slot is refilled with a forward table (table f in slot
     // L - 1 - f)
     static_for<0, L>([&](auto ic) {
@@ -1288,7 +1355,7 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
     // during that wait; the top issued them as its backward sweep freed the slots)
     if (top && !(kDiag && (pl.fault & 4))) TF::issue(SL, pl.fimg + (size_t)(s0 + L - 1) * TFN);
     if (!top) {
-        if (!((pl.fault & 1) && deepest && o == 0)) publish(pl.gq + (size_t)(tt.w0 + o) * G, G, tag, (const ldsu*)XD);
+        if (!((pl.fault & 1) && deepest && o == 0) && !xroot) publish(pl.gq + (size_t)(tt.w0 + o) * G, G, tag, (const ldsu*)XD);
         // k_drc: the CP operands are loaded (older than the forward tables) and go to LDS once
         // they have landed, still inside the wait below
         CpaStage cs;

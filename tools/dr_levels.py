@@ -1,8 +1,8 @@
 """Diagnostics (diagnostic build of the dynamics unit, RAOCP_HIP_LIB=build/var/diag.so): the
 per-level stamps of the first subtree of every tier (raocp_dynr.hip stamp / stamp_flush) for
 the sweep alone (k_dr, the projection op) and inside the fused launch (k_drc), side by side,
-in ns from each launch's earliest stamp: [start, prologue / children's q landed, every backward
-level, backward done, root's x landed, every forward level, forward done, ...] and the end.
+in ns from each launch's earliest stamp: [start, prologue / children's q landed, (a tier with a
+composed root map: its root's q row published,) every backward level, backward done, root's x landed, every forward level, forward done, ...] and the end.
 usage: python tools/dr_levels.py [reps]"""
 import os
 import sys
