@@ -139,7 +139,12 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * space-separated "name@tier" terms: "mid_back_root@k" = tier k (between the top and the
  * deepest) publishes its root's q row from one composed product before its backward levels;
  * "" when none is (RAOCP_DR_XFER=0, a plan with no such tier or with a tier of more than 4
- * levels, another sweep); written NUL-terminated to buf. */
+ * levels, another sweep); op 16: the composed forward maps active in that sweep, in the same
+ * form: "mid_fwd@k" / "deep_fwd@k" = tier k (between the top and the deepest / the deepest)
+ * runs its forward levels from a zero root x row while it waits for that row and adds the
+ * composed map's product with the row once it has landed; "" when none is (RAOCP_DR_XFER=0,
+ * RAOCP_DR_FWD=0, a one-tier plan or one with a tier of more than 4 levels, another sweep);
+ * written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
 /* prox of f on the current primal (Cache.proximal_of_f, cache.py:248-257) and its steps */

@@ -978,8 +978,30 @@ int dr_setup(raocp_ctx* c, const std::vector<double>& WT, int SKP, const std::ve
             p.t[k].xf |= raocp::kDrXfMidBack;
         }
     }
+    // the forward maps: every tier below the top (the deepest included) of binary subtrees with 4
+    // levels sweeps forward from a zero root row inside its wait for that row and adds the
+    // composed map times the row when it lands. RAOCP_DR_FWD=0 switches off these alone.
+    bool fwd = xfer;
+    if (const char* e = getenv("RAOCP_DR_FWD")) fwd = fwd && atoi(e) != 0;
+    std::vector<double> xfw;
+    if (fwd && C == 2 && nx == raocp::kXbNx && nu == raocp::kXbNu && T > 1 && lmax <= 4 && block == raocp::kXfL1) {
+        xfw.assign((size_t)(T - 1) * raocp::kDrXfN, 0.0);
+        for (int k = 1; k < T; ++k) {
+            if (p.t[k].L != raocp::kXbL) continue;
+            raocp::XfStages xs;
+            xs.sab = SKF;
+            xs.skm = SKP;
+            for (int l = 0; l < raocp::kXbL; ++l) {
+                const raocp::Dy3Stage& st = c->reg_st[p.t[k].s0 + l];
+                for (int q = 0; q < 2; ++q) xs.ab[l][q] = &F[(size_t)st.pair[q] * nx * SKF];
+                xs.km[l] = &KM[(size_t)st.cls * nu * SKP];
+            }
+            raocp::xf_pack(raocp::xf_compose(xs), &xfw[(size_t)(k - 1) * raocp::kDrXfN]);
+            p.t[k].xf |= raocp::kDrXfFwd;
+        }
+    }
     int rc;
-    const double *bi = nullptr, *fi = nullptr, *xq = nullptr;
+    const double *bi = nullptr, *fi = nullptr, *xq = nullptr, *xw = nullptr;
     unsigned long long *gq = nullptr, *gx = nullptr;
     unsigned* sy = nullptr;
     c->dr_gran = (size_t)w * 2 * nx;
@@ -992,7 +1014,9 @@ int dr_setup(raocp_ctx* c, const std::vector<double>& WT, int SKP, const std::ve
     if (!xbq.empty() && (rc = c->upload_vec(&xq, xbq))) return rc;
     p.bimg = bi;
     p.fimg = fi;
+    if (!xfw.empty() && (rc = c->upload_vec(&xw, xfw))) return rc;
     p.xbq = xq;
+    p.xfw = xw;
     p.gq = gq;
     p.gx = gx;
     p.sync = sy;
@@ -1063,6 +1087,10 @@ int drc_setup(raocp_ctx* c) {
     a.img = img;
     a.ctl = c->ctl;
     a.box = (bx & 3) == 1 ? 1 : 2;
+    // the unboxed k_drc holds no forward-map step (it does not fit its 128 VGPRs without a
+    // spill): the context's plan, shared with k_dr, keeps the level path there
+    if (a.box == 2)
+        for (int k = 0; k < c->drp.T; ++k) c->drp.t[k].xf &= ~raocp::kDrXfFwd;
     // the launch's arguments in device memory, one copy per iteration parity (part / nanbit)
     {
         raocp::DrcArg two[2] = {a, a};
@@ -1578,6 +1606,14 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             if (c->dr && c->sh_S == 0)
                 for (int k = 0; k < c->drp.T; ++k)
                     if (c->drp.t[k].xf & raocp::kDrXfMidBack) s += (s.empty() ? "" : " ") + std::string("mid_back_root@") + std::to_string(k);
+            return s;
+        }
+        case 16: {  // the composed forward maps of the regular-tree sweep that are active ("" when none)
+            std::string s;
+            if (c->dr && c->sh_S == 0)
+                for (int k = 0; k < c->drp.T; ++k)
+                    if (c->drp.t[k].xf & raocp::kDrXfFwd)
+                        s += (s.empty() ? "" : " ") + std::string(k == c->drp.T - 1 ? "deep_fwd@" : "mid_fwd@") + std::to_string(k);
             return s;
         }
         case 12:  // the forms of the k_cp5 launches, when they run ("" otherwise)
@@ -3150,7 +3186,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }

@@ -24,6 +24,9 @@ struct DrTier {
 // DrTier::xf bit 0: a tier between the top and the deepest publishes its root's q row from the
 // composed map DrPlan::xbq (raocp_drxfer.h) before its backward levels
 constexpr int kDrXfMidBack = 1;
+// bit 1: a tier below the top runs its forward levels from a zero root x row inside its wait for
+// that row and then adds the composed map DrPlan::xfw times the row (raocp_drxfer.h xf_compose)
+constexpr int kDrXfFwd = 2;
 
 // kernel argument of k_dr (passed by value)
 struct DrPlan {
@@ -37,6 +40,7 @@ struct DrPlan {
     const double* bimg;       // backward tables, per nonleaf stage (dr_tb_n doubles each)
     const double* fimg;       // forward tables, per nonleaf stage (dr_tf_n doubles each)
     const double* xbq;        // composed root maps (kDrXbN doubles each): tier k's at (k - 1) kDrXbN
+    const double* xfw;        // composed forward maps (kDrXfN doubles each): tier k's at (k - 1) kDrXfN
     const double* zpage;      // 16 doubles of zeros (LDS-DMA source of padding)
     const double* x0;         // x0bar
     unsigned long long* gq;   // up hand-offs: per slot the root's q row, 2 nx granules {half, tag}

@@ -23,6 +23,9 @@
 //   5. (below the top) waits for its root's x row from the parent subtree (the top takes x0bar),
 //   6. sweeps its levels forward: children's x rows and u_i into LDS,
 //   7. publishes its boundary x rows to the child subtrees, then writes x and u to the iterate.
+// A tier below the top with a composed forward map (XfFwd below) swaps 5. and 6.: it sweeps
+// forward from a zero root x row inside the wait, then waits, adds every row's 20-long dot with
+// the row that landed (the boundary rows first, published behind one barrier) and goes on at 7.
 // Nothing is written to global memory during a sweep, and d never leaves the LDS.
 //
 // A level: lane s of a group holds its table row in registers (one per (row, slot) backward,
@@ -354,6 +357,54 @@ __device__ __forceinline__ void xb_publish(unsigned long long* dst, unsigned tag
         const int r = g >> 1;
         const double q = ((*xb_part(XD, X0B, 3 * r) + *xb_part(XD, X0B, 3 * r + 1)) + *xb_part(XD, X0B, 3 * r + 2)) - XD[r];
         st_gran(dst + g, (g & 1) ? (unsigned)__double2hiint(q) : (unsigned)__double2loint(q), tag);
+    }
+}
+
+// ---- the forward sweep by superposition (raocp_drxfer.h xf_compose; binary subtrees of 4
+// levels at 20 / 8, workgroups of 512 lanes): a tier below the top runs its four forward levels
+// from a zero root x row while it waits for that row, so every x and u row in LDS lacks only its
+// 20-long dot with x_0. Output e of [x of nodes 1..14 | boundary x | u] sits where xb_apply reads
+// its inputs. Step 1: lane t adds one whole output (t < 320: boundary row entry t, published
+// behind the next barrier above the deepest tier; t >= 320: interior output t - 320). Step 2:
+// lanes 2 i, 2 i + 1 < 416 hold the halves of interior output 192 + i and add their DPP sum.
+// Every output has one owner and a fixed order: no atomics, the same bits every run.
+struct XfFwd {
+    d2v w1[kXfP1], w2[kXfP2];
+};
+__device__ __forceinline__ void xf_load(const double* img, XfFwd& m) {
+    const int t = threadIdx.x, t2 = t < kXfL2 ? t : 0;
+    _Pragma("unroll") for (int p = 0; p < kXfP1; ++p) m.w1[p] = *(const glb2*)(img + 2 * ((size_t)p * kXfL1 + t));
+    _Pragma("unroll") for (int p = 0; p < kXfP2; ++p) m.w2[p] = *(const glb2*)(img + kXfOff2 + 2 * ((size_t)p * kXfL2 + t2));
+}
+__device__ __forceinline__ ldsd* xf_out(ldsd* XD, int e) {
+    const int n = e / kXbNx;
+    return XD + (kXbNx + kXbNu) + e + kXbNu * (n < kXbNodes - 1 ? n : kXbNodes - 1);
+}
+template <int P>
+__device__ __forceinline__ double xf_dot(const d2v (&w)[P], const ldsd* x) {
+    d2v a = {0.0, 0.0}, b = {0.0, 0.0};
+    _Pragma("unroll") for (int p = 0; p < P; ++p) {
+        const d2v v = ld2(x + 2 * p);
+        if (p & 1) b += w[p] * v;
+        else a += w[p] * v;
+    }
+    return (a.x + a.y) + (b.x + b.y);
+}
+__device__ __forceinline__ void xf_step1(const XfFwd& m, ldsd* XD) {
+    const int t = threadIdx.x;
+    static_assert(kXfI1 <= kXbXn, "step 1's interior outputs are x rows");
+    const int e = t < kXbQn ? kXbXn + t : t - kXbQn;
+    ldsd* o = xf_out(XD, e);
+    *o += xf_dot<kXfP1>(m.w1, XD);
+}
+__device__ __forceinline__ void xf_step2(const XfFwd& m, ldsd* XD) {
+    const int t = threadIdx.x, i = kXfI1 + (t >> 1);
+    double acc = 0.0;
+    if (t < kXfL2) acc = xf_dot<kXfP2>(m.w2, XD + (t & 1) * (kXbNx / 2));
+    acc += dpp_x<0xB1>(acc);  // lane ^ 1: the other half
+    if (t < kXfL2 && !(t & 1)) {
+        ldsd* o = xf_out(XD, i < kXbXn ? i : i + kXbQn);
+        *o += acc;
     }
 }
 
@@ -1311,6 +1362,11 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
     // (the kernels of plans with at most 4 levels per tier only: UMAX = 1, the 128-VGPR bodies)
     constexpr bool XBC = C == 2 && L == 4 && UMAX == 1 && NX == kXbNx && NU == kXbNu;
     const bool xroot = XBC && !top && !deepest && (tt.xf & kDrXfMidBack) != 0;
+    // the forward map (below the top, the deepest tier included; workgroups of 512 lanes; not
+    // in the unboxed k_drc, whose 128 VGPRs it does not fit without a spill: the host leaves
+    // the bit clear there)
+    constexpr bool XFC = XBC && BS == kXfL1 && BX != 2;
+    const bool xfwd = XFC && !top && (tt.xf & kDrXfFwd) != 0;
     XbRoot xm;
     if constexpr (XBC)
         if (xroot) xb_load(pl.xbq + (size_t)(k - 1) * kDrXbN, xm);
@@ -1371,11 +1427,18 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
                 wait_vm_c<L * TF::IPW>();  // the operands have landed (the forward tables stay in flight)
                 cpa_commit(CPA, cs);
             }
-        if (!poll_gran(pl.gx + (size_t)(tt.w0 + o) * G, G, tag, (ldsu*)XD, pl.timeout, pl.sync, s_ok)) {
-            dma_wait();
-            return;
+        if (xfwd) {
+            // the forward levels run inside the wait, from a zero root x row (the publish above
+            // has read the row before the barrier)
+            lds_sync();
+            if (tid < NX) XD[tid] = 0.0;
+        } else {
+            if (!poll_gran(pl.gx + (size_t)(tt.w0 + o) * G, G, tag, (ldsu*)XD, pl.timeout, pl.sync, s_ok)) {
+                dma_wait();
+                return;
+            }
+            stamp(pl, stp);
         }
-        stamp(pl, stp);
     } else if (tid < NX) {
         XD[tid] = X0B[tid];  // x_0 = x0bar (cache.py:282)
     }
@@ -1402,8 +1465,35 @@ __device__ __forceinline__ void tier_body(const DrPlan& pl, int k, int o, glbd* 
     });
     lds_sync();
     stamp(pl, stp);
+    // ---- 6b. (forward map) the sweep above started from x_0 = 0: once the root's x row has
+    // landed, every row gains its dot with it; the boundary rows first, published behind one
+    // barrier, then the rest
+    if constexpr (XFC)
+        if (xfwd) {
+            // (the map's 30 16-B loads per lane are issued here, not before the levels: 60 VGPRs
+            // across fwd_level do not fit. They, and in k_drc the weight-image DMAs still in
+            // flight, are older than the poll's granule loads in the vmcnt queue, so a row that
+            // has already landed is seen one L2 round trip late)
+            XfFwd fm;
+            xf_load(pl.xfw + (size_t)(k - 1) * kDrXfN, fm);
+            if (!poll_gran(pl.gx + (size_t)(tt.w0 + o) * G, G, tag, (ldsu*)XD, pl.timeout, pl.sync, s_ok)) {
+                dma_wait();
+                return;
+            }
+            stamp(pl, stp);
+            const bool arith = work && !(kDiag && (pl.fault & 16));
+            if (arith) xf_step1(fm, XD);
+            if (!deepest) {
+                lds_sync();
+                publish(pl.gx + (size_t)(pl.t[k + 1].w0 + o * NB) * G, NB * G, tag, (const ldsu*)XL);
+                stamp(pl, stp);
+            }
+            if (arith) xf_step2(fm, XD);
+            lds_sync();
+            stamp(pl, stp);
+        }
     // ---- 7. the boundary x rows to the child subtrees, then x and u to the iterate
-    if (!deepest) publish(pl.gx + (size_t)(pl.t[k + 1].w0 + o * NB) * G, NB * G, tag, (const ldsu*)XL);
+    if (!deepest && !xfwd) publish(pl.gx + (size_t)(pl.t[k + 1].w0 + o * NB) * G, NB * G, tag, (const ldsu*)XL);
     if constexpr (CPF) {
         if (work && gat && top) {  // the top has no wait to hide its operands behind
             CpaStage ct;

@@ -2,7 +2,11 @@
 per-level stamps of the first subtree of every tier (raocp_dynr.hip stamp / stamp_flush) for
 the sweep alone (k_dr, the projection op) and inside the fused launch (k_drc), side by side,
 in ns from each launch's earliest stamp: [start, prologue / children's q landed, (a tier with a
-composed root map: its root's q row published,) every backward level, backward done, root's x landed, every forward level, forward done, ...] and the end.
+composed root map: its root's q row published,) every backward level, backward done, root's x
+landed, every forward level, forward done, ...] and the end. A tier with a composed forward map
+(kernel_info op 16) stamps, behind "backward done": every forward level (of the sweep from a zero
+root row), sweep from zero done, root's x landed, (above the deepest tier) boundary published,
+forward done.
 usage: python tools/dr_levels.py [reps]"""
 import os
 import sys

@@ -1,7 +1,9 @@
 """Diagnostics (a diagnostic build of the dynamics unit: VAR_UNIT=dynr tools/build_var.sh diag
 -DRAOCP_DIAG, then RAOCP_HIP_LIB=build/var/diag.so): where the fused launch k_drc spends its time
 at config 2. Every workgroup stamps its start, the end of its backward sweep, the end of its
-forward sweep (the CP step's start) and its end (raocp_dynr.hip wg_stamp): printed per tier as
+forward sweep (the CP step's start; in a tier with a composed forward map, kernel_info op 16,
+that is behind the map's product with the root's x row, its forward levels having run before
+the row landed) and its end (raocp_dynr.hip wg_stamp): printed per tier as
 min / median / max in ns from the launch's earliest stamp. The first (deepest) and the last (top)
 workgroup also stamp every wave's CP roles (cp_phase dstamp).
 usage: RAOCP_STAMP_KERNEL=f python tools/drc_stamps.py [reps]"""
