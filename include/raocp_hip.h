@@ -135,7 +135,11 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * op 12: the forms of the k_cp5 launches ("leaf_pf=. fams=. fam_pf=.", "" when k_cp5 does not
  * run); op 13: the batched CP kernel of raocp_cp_batch_run ("" when the batch runs as
  * sequential solves); op 14: the step kernel of raocp_cp_batch_mpc ("" when that loop runs on
- * the host); op 15: the composed maps active in the regular-tree sweep (k_dr / k_drc), as
+ * the host); ops 13 and 14 name a kernel on contexts of either precision: "k_cpb<true>" /
+ * "k_cpb<false>" and "k_mpc_step" on an fp64 context (the names the fp64 forms have always
+ * reported), "k_cpb<float, true>" / "k_cpb<float, false>" and "k_mpc_step<float>" on an fp32
+ * one that runs with RAOCP_CPB_F32=1 (the bool: the shared tables are staged in LDS; without
+ * that switch an fp32 context reports "" for both, as it always has); op 15: the composed maps active in the regular-tree sweep (k_dr / k_drc), as
  * space-separated "name@tier" terms: "mid_back_root@k" = tier k (between the top and the
  * deepest) publishes its root's q row from one composed product before its backward levels;
  * "" when none is (RAOCP_DR_XFER=0, a plan with no such tier or with a tier of more than 4
@@ -187,9 +191,16 @@ int raocp_cp_run(raocp_ctx* ctx, const double* x0, int max_iters, double tol, do
  * iterate; both NULL: every instance starts from zero). Each instance runs Solver.chock's loop
  * (solver.py:97-171) with its own stopping test. One launch runs one workgroup per instance
  * (k_cpb, raocp_cpb.hip; chunks of RAOCP_BATCH_CHUNK iterations, default 256, until every
- * instance is done); a context the kernel does not cover (fp32, nx > 32 or nu > 16,
- * RAOCP_CPB=0) runs the B solves one after another through raocp_cp_run, with the same
- * results. Outputs per instance b:
+ * instance is done) in the context's precision. An fp64 context takes the kernel by default;
+ * an fp32 context takes its float form when the environment has RAOCP_CPB_F32=1 (read at call
+ * time; unset, an fp32 context behaves as it always has and runs the sequential solves). On
+ * an fp32 context the slabs, the tables and the arithmetic of a row are float (the residual
+ * maxima are widened to double for the history rows and the stopping test, as raocp_cp_run
+ * does there), and x0, z0, eta0 and the getters below cross the host boundary as fp64 arrays,
+ * converted as the single-solve entry points convert. A context the kernel does not cover
+ * (nx > 32 or nu > 16, RAOCP_CPB=0, fp32 without RAOCP_CPB_F32=1) runs the B solves one after
+ * another through raocp_cp_run, with the same results (fp32: the same up to the rounding of
+ * another summation order). Outputs per instance b:
  *   status[b]  0 converged / 1 not converged / 2 a NaN reached a box projection (that
  *              instance stopped there; the others are not affected)
  *   iters[b]   rows of its error caches
@@ -217,8 +228,10 @@ int raocp_cp_batch_first_inputs(raocp_ctx* ctx, double* u0 /*[B][nu]*/);
  * warm != 0, from this step's final iterate (warm = 0: from zero). One kernel launch per step
  * (k_mpc_step, raocp_cpb.hip) records the step and restarts the instances inside their slabs;
  * besides the done poll of the k_cpb launches nothing crosses the host boundary inside the
- * loop. A context k_cpb does not cover (see raocp_cp_batch_run) runs the same loop on the
- * host over sequential solves, with the same outputs. Outputs:
+ * loop. On an fp32 context the plant step and the stage cost are computed in float (the
+ * root-children table A_i | B_i is held in float) and recorded as doubles. A context k_cpb does
+ * not cover (see raocp_cp_batch_run) runs the same loop on the host over sequential solves, with
+ * the same outputs. Outputs (fp64 arrays and ints on a context of either precision):
  *   X[b][t]       the state step t was solved from (X[b][0] = x0[b]), X[b][T] the last x+
  *   U[b][t]       the input applied, cost[b][t] the realised stage cost
  *   status[b][t]  0 / 1 / 2 and iters[b][t] as raocp_cp_batch_run, err[b][t][0..2] the last row

@@ -972,12 +972,20 @@ int enqueue_cp_iteration(raocp_ctx* c, int it) {
     if (!defer) raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, c->redpart, c->cp_rows, 0, nullptr, nullptr);
     return RAOCP_OK;
 }
-// k_cpb (raocp_cpb.hip) covers this context's batched solves: fp64, unsharded, sizes within
-// the kernel's limits; RAOCP_CPB=0 (read at call time) selects the sequential solves
+// k_cpb (raocp_cpb.hip) covers this context's batched solves: unsharded, sizes within the
+// kernel's limits; RAOCP_CPB=0 (read at call time) selects the sequential solves. An fp64
+// context takes the kernel by default. An fp32 context keeps the sequential solves it has always
+// run unless RAOCP_CPB_F32=1 (read at call time) asks for the float form, which reads the fp32
+// tables of the context's per-stage dynamics (an fp32 context always holds them).
 bool cpb_on(const raocp_ctx* c) {
     const char* e = getenv("RAOCP_CPB");
     if (e && e[0] == '0') return false;
-    return !c->f32 && !c->comm && c->sh_R == 1 && c->nx <= raocp::kCpbMaxNx && c->nu <= raocp::kCpbMaxNu;
+    if (c->f32) {
+        const char* f = getenv("RAOCP_CPB_F32");
+        if (!(f && f[0] == '1')) return false;
+        if (!(c->W2 && c->RG2 && c->KM2 && c->F2)) return false;
+    }
+    return !c->comm && c->sh_R == 1 && c->nx <= raocp::kCpbMaxNx && c->nu <= raocp::kCpbMaxNu;
 }
 void batch_free(raocp_ctx* c) {
     auto& bt = c->bt;
@@ -986,7 +994,8 @@ void batch_free(raocp_ctx* c) {
     if (bt.done) (void)hipFree(bt.done);
     if (bt.hist) (void)hipFree(bt.hist);
     if (bt.u0) (void)hipFree(bt.u0);
-    bt.slab = bt.hist = bt.u0 = nullptr;
+    bt.slab = nullptr;
+    bt.hist = bt.u0 = nullptr;
     bt.ctl = nullptr;
     bt.done = nullptr;
     bt.cap_B = 0;
@@ -1078,9 +1087,9 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             if (!c->cp5) return "";
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
         case 13:  // the batched CP kernel, when raocp_cp_batch_run launches it ("" otherwise)
-            return cpb_on(c) ? raocp::cpb_name(raocp::cpb_tab_bytes(c->dev) > 0) : "";
+            return cpb_on(c) ? raocp::cpb_name(c->f32, raocp::cpb_tab_bytes(c->dev, c->f32) > 0) : "";
         case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
-            return cpb_on(c) ? raocp::mpc_step_name() : "";
+            return cpb_on(c) ? raocp::mpc_step_name(c->f32) : "";
         case 10:
             if (c->cp6 && c->sh_S == 0) return raocp::cp6_name();
             if (c->cp5) return std::string(raocp::cp5_name(c->f32, c->nx)) + (c->sh_S > 0 ? " (+ fams x1 after X1)" : "");
@@ -1722,8 +1731,8 @@ int batch_ensure(raocp_ctx* c, int B, size_t rows) {
     if (bt.cap_B == B && rows <= bt.hist_rows) return RAOCP_OK;
     const size_t want = std::max(rows, bt.cap_B == B ? bt.hist_rows : (size_t)0);
     batch_free(c);
-    bt.lay = raocp::cpb_layout(c->dev);
-    HIPCHK(hipMalloc((void**)&bt.slab, (size_t)B * bt.lay.stride * sizeof(double)));
+    bt.lay = raocp::cpb_layout(c->dev, c->f32);
+    HIPCHK(hipMalloc((void**)&bt.slab, (size_t)B * bt.lay.stride * c->wsz));
     HIPCHK(hipMalloc((void**)&bt.ctl, (size_t)B * sizeof(Ctl)));
     HIPCHK(hipMalloc((void**)&bt.done, (size_t)B * sizeof(int)));
     HIPCHK(hipMalloc((void**)&bt.hist, (size_t)B * want * 6 * sizeof(double)));
@@ -1733,11 +1742,44 @@ int batch_ensure(raocp_ctx* c, int B, size_t rows) {
     return RAOCP_OK;
 }
 
-// rows of `width` doubles, one per instance, into the slabs at offset `off`
+// rows of `width` host doubles, one per instance, into the slabs at element offset `off` (an
+// fp32 context converts on the host, as copy_in does)
 int batch_scatter(raocp_ctx* c, long off, const double* src, size_t width, int B) {
-    HIPCHK(hipMemcpy2DAsync(c->bt.slab + off, (size_t)c->bt.lay.stride * sizeof(double), src, width * sizeof(double),
-                            width * sizeof(double), (size_t)B, hipMemcpyHostToDevice, c->stream));
+    const size_t w = (size_t)c->wsz;
+    char* dst = c->bt.slab + (size_t)off * w;
+    if (c->f32) {
+        const std::vector<float> tmp(src, src + width * (size_t)B);
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->bt.lay.stride * w, tmp.data(), width * w, width * w, (size_t)B,
+                                hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return RAOCP_OK;
+    }
+    HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->bt.lay.stride * w, src, width * w, width * w, (size_t)B, hipMemcpyHostToDevice,
+                            c->stream));
     return RAOCP_OK;
+}
+
+// the kernel arguments of a batch of B instances with `rows` history rows each
+raocp::CpbArg batch_arg(raocp_ctx* c, int B, size_t rows) {
+    auto& bt = c->bt;
+    raocp::CpbArg a{};
+    a.slab = bt.slab;
+    a.lay = bt.lay;
+    a.ctl = bt.ctl;
+    a.done = bt.done;
+    a.hist = bt.hist;
+    a.hist_rows = (long)rows;
+    a.u0 = bt.u0;
+    a.B = B;
+    a.chunk = batch_chunk();
+    a.lds_tabs = raocp::cpb_tab_bytes(c->dev, c->f32) > 0 ? 1 : 0;
+    if (c->f32) {
+        a.W2 = c->W2;
+        a.RG2 = c->RG2;
+        a.KM2 = c->KM2;
+        a.F2 = c->F2;
+    }
+    return a;
 }
 
 int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
@@ -1747,7 +1789,7 @@ int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, co
     int rc;
     if ((rc = batch_ensure(c, B, rows))) return rc;
     const raocp::CpbSlab& L = bt.lay;
-    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * c->wsz, c->stream));
     HIPCHK(hipMemsetAsync(bt.done, 0, (size_t)B * sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(bt.u0, 0, (size_t)B * c->nu * sizeof(double), c->stream));
     if (z0) {
@@ -1764,22 +1806,12 @@ int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, co
     h.tol = tol;
     std::vector<Ctl> hc((size_t)B, h);
     HIPCHK(hipMemcpyAsync(bt.ctl, hc.data(), hc.size() * sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
-    raocp::CpbArg a{};
-    a.slab = bt.slab;
-    a.lay = L;
-    a.ctl = bt.ctl;
-    a.done = bt.done;
-    a.hist = bt.hist;
-    a.hist_rows = (long)rows;
-    a.u0 = bt.u0;
-    a.B = B;
-    a.chunk = batch_chunk();
-    a.lds_tabs = raocp::cpb_tab_bytes(c->dev) > 0 ? 1 : 0;
+    const raocp::CpbArg a = batch_arg(c, B, rows);
     std::vector<int> hd((size_t)B, 0);
     const long launches = (long)(rows + a.chunk - 1) / a.chunk + 1;  // every instance ends within rows iterations
     bool all = false;
     for (long l = 0; l < launches && !all; ++l) {
-        HIPCHK(raocp::cpb_launch(c->dev, a, c->stream));
+        HIPCHK(raocp::cpb_launch(c->dev, a, c->f32, c->stream));
         HIPCHK(hipMemcpyAsync(hd.data(), bt.done, hd.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         all = std::all_of(hd.begin(), hd.end(), [](int v) { return v != 0; });
@@ -1928,12 +1960,12 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
     const size_t rows = (size_t)max_iters + 1, BT = (size_t)B * T;
     int rc;
     if (c->h_mpc_ab.empty()) return fail(RAOCP_ERR_STATE, "no plant tables for the root's children");
-    if (!c->d_mpc_ab && (rc = c->upload(&c->d_mpc_ab, c->h_mpc_ab.data(), c->h_mpc_ab.size()))) return rc;
+    if (!c->d_mpc_ab && (rc = upload_t(c, &c->d_mpc_ab, c->h_mpc_ab))) return rc;
     if ((rc = batch_ensure(c, B, rows))) return rc;
     MpcBufs mb{};
     if ((rc = mpc_ensure(c, B, T, &mb))) return rc;
     const raocp::CpbSlab& L = bt.lay;
-    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * c->wsz, c->stream));
     HIPCHK(hipMemsetAsync(bt.done, 0, (size_t)B * sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(bt.u0, 0, (size_t)B * c->nu * sizeof(double), c->stream));
     HIPCHK(hipMemsetAsync(mb.frz, 0xff, (size_t)B * sizeof(int), c->stream));  // -1: running
@@ -1947,17 +1979,7 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
     h.tol = tol;
     const std::vector<Ctl> hc((size_t)B, h);
     HIPCHK(hipMemcpyAsync(bt.ctl, hc.data(), hc.size() * sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
-    raocp::CpbArg a{};
-    a.slab = bt.slab;
-    a.lay = L;
-    a.ctl = bt.ctl;
-    a.done = bt.done;
-    a.hist = bt.hist;
-    a.hist_rows = (long)rows;
-    a.u0 = bt.u0;
-    a.B = B;
-    a.chunk = batch_chunk();
-    a.lds_tabs = raocp::cpb_tab_bytes(c->dev) > 0 ? 1 : 0;
+    const raocp::CpbArg a = batch_arg(c, B, rows);
     raocp::MpcArg m{};
     m.ab = c->d_mpc_ab;
     m.scen = mb.scen;
@@ -1975,7 +1997,7 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
     for (int t = 0; t < T; ++t) {
         bool all = false;
         for (long l = 0; l < launches && !all; ++l) {
-            HIPCHK(raocp::cpb_launch(c->dev, a, c->stream));
+            HIPCHK(raocp::cpb_launch(c->dev, a, c->f32, c->stream));
             HIPCHK(hipMemcpyAsync(hd.data(), bt.done, hd.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
             all = std::all_of(hd.begin(), hd.end(), [](int v) { return v != 0; });
@@ -1983,7 +2005,7 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
         if (!all) return fail(RAOCP_ERR_STATE, "batched CP kernel: an instance did not finish");
         m.t = t;
         m.last = t == T - 1 ? 1 : 0;
-        HIPCHK(raocp::mpc_step_launch(c->dev, a, m, c->stream));
+        HIPCHK(raocp::mpc_step_launch(c->dev, a, m, c->f32, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(X, mb.X, (size_t)B * (T + 1) * c->nx * sizeof(double), hipMemcpyDeviceToHost));
@@ -2124,11 +2146,13 @@ int raocp_cp_batch_get(raocp_ctx* c, int b, double* z, double* eta) {
         std::copy(bt.he.begin() + (size_t)b * c->D, bt.he.begin() + (size_t)(b + 1) * c->D, eta);
         return RAOCP_OK;
     }
-    const double* slab = bt.slab + (size_t)b * bt.lay.stride;
+    // the slab holds the context's scalar type; an fp32 context widens on the host (copy_out)
+    const size_t w = (size_t)c->wsz;
+    const char* slab = bt.slab + (size_t)b * bt.lay.stride * w;
     const int fk = bt.fk[b];
-    HIPCHK(hipMemcpy(z, slab + bt.lay.z[(fk + 1) % 3], (size_t)c->P * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(eta, slab + bt.lay.e[(fk + 1) % 2], (size_t)c->D * sizeof(double), hipMemcpyDeviceToHost));
-    return RAOCP_OK;
+    int rc;
+    if ((rc = copy_out(c, z, (const double*)(slab + (size_t)bt.lay.z[(fk + 1) % 3] * w), (size_t)c->P, 0))) return rc;
+    return copy_out(c, eta, (const double*)(slab + (size_t)bt.lay.e[(fk + 1) % 2] * w), (size_t)c->D, 0);
 }
 
 int raocp_cp_batch_first_inputs(raocp_ctx* c, double* u0) {

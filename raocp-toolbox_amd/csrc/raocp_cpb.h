@@ -4,6 +4,7 @@
 #pragma once
 
 #include "raocp_common.h"
+#include "raocp_cpb_layout.h"
 
 namespace raocp {
 
@@ -12,22 +13,11 @@ constexpr int kCpbMaxNx = 32;         // runtime sizes the kernel covers
 constexpr int kCpbMaxNu = 16;
 constexpr int kCpbLdsTabs = 32 * 1024;  // LDS budget of the staged tables (bytes): >= 4 workgroups per CU
 
-// one instance's slab in HBM: offsets in doubles from the slab's start, every array on a 16-B
-// boundary, `stride` doubles (a multiple of 32: 256 B) between the slabs of two instances
-struct CpbSlab {
-    long z[3];    // the rotating primals (P each)
-    long e[2];    // the rotating duals (D each)
-    long xi2;     // xi2 (D)
-    long tv;      // the dual half step v before its projection (D)
-    long q;       // q rows of the dynamics projection (n x nx)
-    long dd;      // d rows (m x nu)
-    long pb;      // child products [h | a] (n x (nu + nx))
-    long x0;      // the instance's initial state (nx)
-    long stride;
-};
-
+// The kernels are templates on the context's scalar type T (double, or float on an fp32
+// context): the slabs, the shared tables and the root-children table of MpcArg hold T; the
+// control blocks, the history rows, u0 and the records of MpcArg are double / int for either T.
 struct CpbArg {
-    double* slab;      // [B] slabs
+    void* slab;        // [B] slabs of T (CpbSlab offsets are in elements of T)
     CpbSlab lay;
     Ctl* ctl;          // [B] control blocks (pad: 1 once the first half step is done)
     int* done;         // [B] the done words the host polls
@@ -37,12 +27,18 @@ struct CpbArg {
     int B;
     int chunk;         // CP iterations per launch
     int lds_tabs;      // the L weights and the box tables are staged in LDS
+    // T = float only: the dynamics tables as an fp32 context holds them (the column-major
+    // M[k rows + r] tables of its per-stage dynamics: W, RG, K, F; Dev's dW .. dF are fp64)
+    const void* W2;
+    const void* RG2;
+    const void* KM2;
+    const void* F2;
 };
 
 // k_mpc_step: the end of one closed-loop MPC step of a batch and the start of the next, inside
 // the slabs (after every instance of the batch is done with step t)
 struct MpcArg {
-    const double* ab;    // [nch[0]] {A_i (nx x nx) | B_i (nx x nu)} row-major, i = ch_start[0] + j
+    const void* ab;      // T [nch[0]] {A_i (nx x nx) | B_i (nx x nu)} row-major, i = ch_start[0] + j
     const int* scen;     // [B][T] realised root child j of instance b at step t
     int* frz;            // [B] the step at which the instance froze (NaN in a box), -1: running
     double* X;           // [B][T + 1][nx]
@@ -57,12 +53,16 @@ struct MpcArg {
     int last;            // t == T - 1: record only, the slab keeps the last solve
 };
 
-CpbSlab cpb_layout(const Dev& p);
-// bytes of LDS the staged tables take, 0 when they exceed kCpbLdsTabs (then read from HBM)
-size_t cpb_tab_bytes(const Dev& p);
-hipError_t cpb_launch(const Dev& p, const CpbArg& a, hipStream_t stream);
-const char* cpb_name(bool lds_tabs);
-hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, hipStream_t stream);
-const char* mpc_step_name();
+// f32: the context's scalar type is float (its Dev tables hold floats)
+CpbSlab cpb_layout(const Dev& p, bool f32);
+// bytes of LDS the staged tables take in the context's type, 0 when they exceed kCpbLdsTabs
+// (then read from HBM)
+size_t cpb_tab_bytes(const Dev& p, bool f32);
+hipError_t cpb_launch(const Dev& p, const CpbArg& a, bool f32, hipStream_t stream);
+// the names raocp_kernel_info reports: the fp64 forms keep the strings they had before the
+// kernels took a type ("k_cpb<true>", "k_mpc_step"), the fp32 forms name it
+const char* cpb_name(bool f32, bool lds_tabs);
+hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, bool f32, hipStream_t stream);
+const char* mpc_step_name(bool f32);
 
 }  // namespace raocp

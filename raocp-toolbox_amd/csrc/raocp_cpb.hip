@@ -22,6 +22,13 @@
 // The arithmetic of a row is that of the node-block kernels (raocp_cp.hip) and of the per-stage
 // dynamics (raocp_dyn.hip: the same tables W, RG, KM, F of Dev with their padded row strides).
 //
+// Precision. The kernels are templates on the context's scalar type T (double or float): the
+// slab, the tables and every row's FMA chain are T, nothing is promoted inside a row. An fp32
+// context's tables are read as it holds them: Dev's L weights, box bounds, alpha_r and cond are
+// floats there, and the dynamics tables are its column-major fp32 W2, RG2, KM2, F2 (CpbArg).
+// The control block, the history rows, u0 and the records of k_mpc_step are double / int for
+// either T (converted at the store); the stopping test compares in double.
+//
 // Memory. The instance's state (three primals, two duals, xi2, v, q, d, the child products)
 // lives in its slab in HBM (CpbSlab); the slab of the main.py problem is a few KiB, so it stays
 // in the L2 of the XCD the workgroup runs on. The tables every instance shares (sqrt Q, sqrt R,
@@ -32,9 +39,20 @@
 namespace raocp {
 namespace {
 
-typedef const glbd* cgd;
-typedef const ldsd* cld;
+// explicit address spaces for either scalar type: global_load / ds_read, never flat
+template <class T>
+using gl = __attribute__((address_space(1))) T;
+template <class T>
+using cg = const __attribute__((address_space(1))) T*;
+template <class T>
+using cl = const __attribute__((address_space(3))) T*;
 typedef __attribute__((address_space(1))) const int glbi;
+
+// max for the residual reductions in T: a NaN operand wins (raocp_common.h nmax)
+template <class T>
+__device__ __forceinline__ T nmx(T a, T b) {
+    return (a > b || a != a) ? a : b;
+}
 
 constexpr __host__ __device__ int rup_(int a, int b) { return (a + b - 1) / b * b; }
 // the row strides of the dynamics tables (raocp_dyn.hip tstride)
@@ -45,14 +63,16 @@ __device__ __forceinline__ int e4(const Dev& p, int j) { return p.E4 + 1 + (j - 
 __device__ __forceinline__ int e11(const Dev& p, int l) { return p.E11 + p.m + (l - p.m) * p.nx; }
 
 // SecondOrderCone.project (cones.py:113-132) for one coordinate of the block
-__device__ __forceinline__ double soc_apply(double v, bool is_t, double nf, double t) {
+template <class T>
+__device__ __forceinline__ T soc_apply(T v, bool is_t, T nf, T t) {
     if (nf <= t) return v;
-    if (nf <= -t) return 0.0;
-    const double s = (nf + t) / 2.0;
+    if (nf <= -t) return T(0);
+    const T s = (nf + t) / T(2);
     return is_t ? s : s * (v / nf);
 }
 // Rectangle._constrain (rectangle.py:50-59); a NaN stays and raises the lane's flag
-__device__ __forceinline__ double box_apply(double v, double lo, double hi, bool& nan) {
+template <class T>
+__device__ __forceinline__ T box_apply(T v, T lo, T hi, bool& nan) {
     if (lo <= v && v <= hi) return v;
     if (v <= lo) return lo;
     if (v >= hi) return hi;
@@ -60,53 +80,55 @@ __device__ __forceinline__ double box_apply(double v, double lo, double hi, bool
     return v;
 }
 
-// the tables every instance shares, in LDS (PT = cld) or in HBM (PT = cgd)
+// the tables every instance shares, in LDS (PT = cl<T>) or in HBM (PT = cg<T>)
 template <class PT>
 struct Tabs {
     PT SQ, SR, SP, BLn, BHn, BLl, BHl;
 };
 
 // one instance's arrays for iteration k
+template <class T>
 struct View {
-    glbd* pz;   // p = Z[k % 3]
-    glbd* zp;   // z+ = Z[(k + 1) % 3]
-    glbd* out;  // Z[(k + 2) % 3]
-    glbd* d;    // E[k % 2]
-    glbd* eo;   // eta+ = E[(k + 1) % 2]
-    glbd* xi2;
-    glbd* tv;
-    glbd* q;
-    glbd* dd;
-    glbd* pb;
-    cgd x0;
+    gl<T>* pz;   // p = Z[k % 3]
+    gl<T>* zp;   // z+ = Z[(k + 1) % 3]
+    gl<T>* out;  // Z[(k + 2) % 3]
+    gl<T>* d;    // E[k % 2]
+    gl<T>* eo;   // eta+ = E[(k + 1) % 2]
+    gl<T>* xi2;
+    gl<T>* tv;
+    gl<T>* q;
+    gl<T>* dd;
+    gl<T>* pb;
+    cg<T> x0;
 };
 
+template <class T>
 struct Maxima {
-    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0, m5 = 0.0;
+    T m0 = T(0), m1 = T(0), m2 = T(0), m3 = T(0), m4 = T(0), m5 = T(0);
     // one primal entry: pp = p, zz = z+, w = L^T(d - eta+), lc = L^T xi2
-    __device__ __forceinline__ void account(double alpha, double pp, double zz, double w, double lc) {
-        const double x1 = (pp - zz) / alpha - w;
-        const double x0v = x1 + lc;
-        const double dl1 = zz - pp;
-        const double dl0 = dl1 + w;
-        m0 = nmax(m0, fabs(x0v));
-        m1 = nmax(m1, fabs(x1));
-        m3 = nmax(m3, fabs(dl0));
-        m4 = nmax(m4, fabs(dl1));
+    __device__ __forceinline__ void account(T alpha, T pp, T zz, T w, T lc) {
+        const T x1 = (pp - zz) / alpha - w;
+        const T x0v = x1 + lc;
+        const T dl1 = zz - pp;
+        const T dl0 = dl1 + w;
+        m0 = nmx<T>(m0, fabs(x0v));
+        m1 = nmx<T>(m1, fabs(x1));
+        m3 = nmx<T>(m3, fabs(dl0));
+        m4 = nmx<T>(m4, fabs(dl1));
     }
 };
 
 // ---- the primal half step from the dual dA (FULL: eta+, with the residuals of the iteration;
 // else the solve's first half step from d): src - alpha L^T dA, s_0 -= alpha, kernel projection
-template <bool FULL, class PT>
-__device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, const View& v, glbd* out, double alpha,
-                                             Maxima& mx, int tid, int nthr) {
+template <class T, bool FULL, class PT>
+__device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, const View<T>& v, gl<T>* out, T alpha,
+                                             Maxima<T>& mx, int tid, int nthr) {
     const int nx = p.nx, nu = p.nu, R = nx + nu;
-    cgd pz = v.pz;
-    cgd src = FULL ? v.zp : v.pz;
-    cgd dA = FULL ? v.eo : v.d;
-    cgd dP = v.d;
-    cgd xg = v.xi2;
+    cg<T> pz = v.pz;
+    cg<T> src = FULL ? v.zp : v.pz;
+    cg<T> dA = FULL ? v.eo : v.d;
+    cg<T> dP = v.d;
+    cg<T> xg = v.xi2;
     glbrec* frec = (glbrec*)p.frec;
     glbrec* crec = (glbrec*)p.crec;
     glbrec* lrec = (glbrec*)p.lrec;
@@ -116,7 +138,7 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
         const bool isx = r < nx;
         const int rr = isx ? r : r - nx;
         const Rec fr = frec[i];
-        double accA = 0.0, accW = 0.0, accC = 0.0;
+        T accA = T(0), accW = T(0), accC = T(0);
         if (fr.w >= 0) {
             const int o = fr.w + r;
             accA = dA[o];
@@ -131,9 +153,9 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
             const int len = isx ? nx : nu;
             const PT M = isx ? tb.SQ + (size_t)cr.y * nx * nx + rr : tb.SR + (size_t)cr.z * nu * nu + rr;
             const int o = isx ? e3(p, j) : e4(p, j);
-            double sA = 0.0, sW = 0.0, sC = 0.0;
+            T sA = T(0), sW = T(0), sC = T(0);
             for (int k = 0; k < len; ++k) {
-                const double mk = M[k * len], va = dA[o + k];
+                const T mk = M[k * len], va = dA[o + k];
                 sA = fma(mk, va, sA);
                 if (FULL) {
                     sW = fma(mk, dP[o + k] - va, sW);
@@ -145,7 +167,7 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
             accC += sC;
         }
         const int e = isx ? p.X0 + i * nx + rr : p.U0 + i * nu + rr;
-        const double zz = src[e];
+        const T zz = src[e];
         out[e] = zz - alpha * accA;
         if (FULL) mx.account(alpha, pz[e], zz, accW, accC);
     }
@@ -155,9 +177,9 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
         const Rec lr = lrec[ll];
         const PT M = tb.SP + (size_t)lr.x * nx * nx + r;
         const int o = e11(p, l);
-        double sA = 0.0, sW = 0.0, sC = 0.0;
+        T sA = T(0), sW = T(0), sC = T(0);
         for (int k = 0; k < nx; ++k) {
-            const double mk = M[k * nx], va = dA[o + k];
+            const T mk = M[k * nx], va = dA[o + k];
             sA = fma(mk, va, sA);
             if (FULL) {
                 sW = fma(mk, dP[o + k] - va, sW);
@@ -173,7 +195,7 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
             }
         }
         const int e = p.X0 + l * nx + r;
-        const double zz = src[e];
+        const T zz = src[e];
         out[e] = zz - alpha * sA;
         if (FULL) mx.account(alpha, pz[e], zz, sW, sC);
     }
@@ -182,44 +204,44 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
     for (int i = tid; i < p.m; i += nthr) {
         const Rec fr = frec[i];
         const int c = fr.y, cs = fr.z, yo = p.Y0 + fr.x, e1o = p.E1 + fr.x;
-        const double al = ((cgd)p.alpha_r)[i];
-        const double e2A = dA[p.E2 + i];
-        double e2W = 0.0, e2C = 0.0;
+        const T al = ((cg<T>)p.alpha_r)[i];
+        const T e2A = dA[p.E2 + i];
+        T e2W = T(0), e2C = T(0);
         if (FULL) {
             e2W = dP[p.E2 + i] - e2A;
             e2C = xg[p.E2 + i];
         }
         const int f2 = 2 * c;
-        double y2c = src[yo + f2] - alpha * (dA[e1o + f2] - 1.0 * e2A);
-        if (FULL) mx.account(alpha, pz[yo + f2], src[yo + f2], (dP[e1o + f2] - dA[e1o + f2]) - 1.0 * e2W, xg[e1o + f2] - 1.0 * e2C);
+        T y2c = src[yo + f2] - alpha * (dA[e1o + f2] - T(1) * e2A);
+        if (FULL) mx.account(alpha, pz[yo + f2], src[yo + f2], (dP[e1o + f2] - dA[e1o + f2]) - T(1) * e2W, xg[e1o + f2] - T(1) * e2C);
         if (i == 0) {
-            const double z0s = src[p.S0];
+            const T z0s = src[p.S0];
             out[p.S0] = (z0s - alpha * e2A) - alpha;
             if (FULL) mx.account(alpha, pz[p.S0], z0s, e2W, e2C);
         }
-        double sr = 0.0;
+        T sr = T(0);
         for (int q = 0; q < c; ++q) {
             const int j = cs + q, f0 = q, f1 = c + q;
-            const double b = ((cgd)p.cond)[j];
-            const double lt0 = dA[e1o + f0] - b * e2A, lt1 = dA[e1o + f1] - 0.0 * e2A;
-            const double v0 = src[yo + f0] - alpha * lt0;
-            const double v1 = src[yo + f1] - alpha * lt1;
-            const double ltt = 0.5 * (dA[p.E5 + j] + dA[p.E6 + j]);
-            const double v2 = src[p.T0 + j] - alpha * ltt;
-            const double lts = j < p.m ? dA[p.E2 + j] : 0.5 * (dA[p.E12 + j] + dA[p.E13 + j]);
-            const double v3 = src[p.S0 + j] - alpha * lts;
+            const T b = ((cg<T>)p.cond)[j];
+            const T lt0 = dA[e1o + f0] - b * e2A, lt1 = dA[e1o + f1] - T(0) * e2A;
+            const T v0 = src[yo + f0] - alpha * lt0;
+            const T v1 = src[yo + f1] - alpha * lt1;
+            const T ltt = T(0.5) * (dA[p.E5 + j] + dA[p.E6 + j]);
+            const T v2 = src[p.T0 + j] - alpha * ltt;
+            const T lts = j < p.m ? dA[p.E2 + j] : T(0.5) * (dA[p.E12 + j] + dA[p.E13 + j]);
+            const T v3 = src[p.S0 + j] - alpha * lts;
             if (FULL) {
-                const double w0 = (dP[e1o + f0] - dA[e1o + f0]) - b * e2W, c0 = xg[e1o + f0] - b * e2C;
-                const double w1 = (dP[e1o + f1] - dA[e1o + f1]) - 0.0 * e2W, c1 = xg[e1o + f1] - 0.0 * e2C;
-                const double wt = 0.5 * ((dP[p.E5 + j] - dA[p.E5 + j]) + (dP[p.E6 + j] - dA[p.E6 + j]));
-                const double ct = 0.5 * (xg[p.E5 + j] + xg[p.E6 + j]);
-                double ws, cs2;
+                const T w0 = (dP[e1o + f0] - dA[e1o + f0]) - b * e2W, c0 = xg[e1o + f0] - b * e2C;
+                const T w1 = (dP[e1o + f1] - dA[e1o + f1]) - T(0) * e2W, c1 = xg[e1o + f1] - T(0) * e2C;
+                const T wt = T(0.5) * ((dP[p.E5 + j] - dA[p.E5 + j]) + (dP[p.E6 + j] - dA[p.E6 + j]));
+                const T ct = T(0.5) * (xg[p.E5 + j] + xg[p.E6 + j]);
+                T ws, cs2;
                 if (j < p.m) {
                     ws = dP[p.E2 + j] - dA[p.E2 + j];
                     cs2 = xg[p.E2 + j];
                 } else {
-                    ws = 0.5 * ((dP[p.E12 + j] - dA[p.E12 + j]) + (dP[p.E13 + j] - dA[p.E13 + j]));
-                    cs2 = 0.5 * (xg[p.E12 + j] + xg[p.E13 + j]);
+                    ws = T(0.5) * ((dP[p.E12 + j] - dA[p.E12 + j]) + (dP[p.E13 + j] - dA[p.E13 + j]));
+                    cs2 = T(0.5) * (xg[p.E12 + j] + xg[p.E13 + j]);
                 }
                 mx.account(alpha, pz[yo + f0], src[yo + f0], w0, c0);
                 mx.account(alpha, pz[yo + f1], src[yo + f1], w1, c1);
@@ -232,13 +254,13 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
             out[p.S0 + j] = v3;
             sr += al * v0 - v1 + y2c - v2 - v3;
         }
-        const double a = al * al + 3.0;
-        double sw = 0.0;
+        const T a = al * al + T(3);
+        T sw = T(0);
         for (int q = 0; q < c; ++q) {
             const int j = cs + q, f0 = q, f1 = c + q;
-            const double v0 = out[yo + f0], v1 = out[yo + f1], v2 = out[p.T0 + j], v3 = out[p.S0 + j];
-            const double rk = al * v0 - v1 + y2c - v2 - v3;
-            const double w = (rk - sr / (a + (double)c)) / a;
+            const T v0 = out[yo + f0], v1 = out[yo + f1], v2 = out[p.T0 + j], v3 = out[p.S0 + j];
+            const T rk = al * v0 - v1 + y2c - v2 - v3;
+            const T w = (rk - sr / (a + (T)c)) / a;
             out[yo + f0] = v0 - al * w;
             out[yo + f1] = v1 + w;
             out[p.T0 + j] = v2 + w;
@@ -250,13 +272,38 @@ __device__ __forceinline__ void primal_phase(const Dev& p, const Tabs<PT>& tb, c
 }
 
 // ---- projection of (x, u) of z onto the dynamics (cache.py:259-288), stage by stage
-__device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd* z, int tid, int nthr) {
+// The dynamics tables as the context holds them. double: Dev's row-major W, RG, KM, F with the
+// padded row strides of raocp_dyn.hip (entry k of a row at [k]). float: the fp32 context's
+// column-major M[k rows + r] tables of its per-stage dynamics (CpbArg W2 .. F2; entry k of row r
+// at [k rows], so the lanes of consecutive rows read consecutive words).
+template <class T>
+struct DynRow {
+    cg<T> ptr;
+    int step;
+    __device__ __forceinline__ T operator[](int k) const { return ptr[k * step]; }
+};
+template <class T>
+__device__ __forceinline__ void dynamics_phase(const Dev& p, const CpbArg& a, const View<T>& v, gl<T>* z, int tid, int nthr) {
+    constexpr bool COL = std::is_same<T, float>::value;
     const int nx = p.nx, nu = p.nu, R = nx + nu;
     const int SKP = tstride_(rup_(nx, 8)), SKF = tstride_(rup_(nx + nu, 8)), SNU = tstride_(rup_(nu, 2));
     glbrec* ninfo = (glbrec*)p.ninfo;
     glbrec* cinfo = (glbrec*)p.cinfo;
     glbi* sp = (glbi*)p.stage_ptr;
-    cgd W = (cgd)p.dW, RG = (cgd)p.dRG, KM = (cgd)p.dKM, F = (cgd)p.dF;
+    cg<T> W = (cg<T>)(COL ? a.W2 : (const void*)p.dW), RG = (cg<T>)(COL ? a.RG2 : (const void*)p.dRG);
+    cg<T> KM = (cg<T>)(COL ? a.KM2 : (const void*)p.dKM), F = (cg<T>)(COL ? a.F2 : (const void*)p.dF);
+    auto row_w = [&](int kind, int rho) {
+        return COL ? DynRow<T>{W + (size_t)kind * nx * R + rho, R} : DynRow<T>{W + ((size_t)kind * R + rho) * SKP, 1};
+    };
+    auto row_rg = [&](int cls, int tr) {
+        return COL ? DynRow<T>{RG + (size_t)cls * nu * R + tr, R} : DynRow<T>{RG + ((size_t)cls * R + tr) * SNU, 1};
+    };
+    auto row_km = [&](int cls, int r) {
+        return COL ? DynRow<T>{KM + (size_t)cls * nx * nu + r, nu} : DynRow<T>{KM + ((size_t)cls * nu + r) * SKP, 1};
+    };
+    auto row_f = [&](int pair, int r) {
+        return COL ? DynRow<T>{F + (size_t)pair * R * nx + r, nx} : DynRow<T>{F + ((size_t)pair * nx + r) * SKF, 1};
+    };
     for (int t = p.N - 1; t >= 0; --t) {
         const int b = sp[t], e = min((int)sp[t + 1], p.m);
         if (b >= e) continue;  // uniform over the workgroup
@@ -266,9 +313,9 @@ __device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd
         for (int it = tid; it < (ce - cb) * R; it += nthr) {
             const int jj = it / R, rho = it - jj * R, j = cb + jj;
             const Rec cj = cinfo[j];
-            cgd w = W + ((size_t)cj.x * R + rho) * SKP;
-            cgd qv = j < p.m ? (cgd)v.q + (size_t)j * nx : (cgd)z + p.X0 + (size_t)j * nx;
-            double acc = 0.0;
+            const DynRow<T> w = row_w(cj.x, rho);
+            cg<T> qv = j < p.m ? (cg<T>)v.q + (size_t)j * nx : (cg<T>)z + p.X0 + (size_t)j * nx;
+            T acc = T(0);
             for (int k = 0; k < nx; ++k) acc = fma(w[k], qv[k], acc);
             v.pb[(size_t)j * R + rho] = j < p.m ? acc : -acc;
         }
@@ -277,11 +324,11 @@ __device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd
         for (int it = tid; it < (e - b) * R; it += nthr) {
             const int ii = it / R, tr = it - ii * R, i = b + ii;
             const Rec ni = ninfo[i];
-            cgd rg = RG + ((size_t)ni.z * R + tr) * SNU;
-            cgd u = (cgd)z + p.U0 + (size_t)i * nu;
-            double s = 0.0;
+            const DynRow<T> rg = row_rg(ni.z, tr);
+            cg<T> u = (cg<T>)z + p.U0 + (size_t)i * nu;
+            T s = T(0);
             for (int k = 0; k < nu; ++k) {
-                double vk = u[k];
+                T vk = u[k];
                 for (int q = 0; q < ni.y; ++q) vk -= v.pb[(size_t)(ni.x + q) * R + k];
                 s = fma(rg[k], vk, s);
             }
@@ -289,7 +336,7 @@ __device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd
                 v.dd[(size_t)i * nu + tr] = s;
             } else {
                 const int r = tr - nu;
-                double a = 0.0;
+                T a = T(0);
                 for (int q = 0; q < ni.y; ++q) a += v.pb[(size_t)(ni.x + q) * R + nu + r];
                 v.q[(size_t)i * nx + r] = (-z[p.X0 + (size_t)i * nx + r] + a) + s;
             }
@@ -308,18 +355,18 @@ __device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd
             if (it < nU) {
                 const int ii = it / nu, r = it - ii * nu, i = b + ii;
                 const Rec ni = ninfo[i];
-                cgd km = KM + ((size_t)ni.z * nu + r) * SKP;
-                cgd x = (cgd)z + p.X0 + (size_t)i * nx;
-                double s = 0.0;
+                const DynRow<T> km = row_km(ni.z, r);
+                cg<T> x = (cg<T>)z + p.X0 + (size_t)i * nx;
+                T s = T(0);
                 for (int k = 0; k < nx; ++k) s = fma(km[k], x[k], s);
                 z[p.U0 + (size_t)i * nu + r] = s + v.dd[(size_t)i * nu + r];
             } else {
                 const int wi = it - nU, jj = wi / nx, r = wi - jj * nx, j = cb + jj;
                 const Rec cj = cinfo[j];
-                cgd f = F + ((size_t)cj.y * nx + r) * SKF;
-                cgd x = (cgd)z + p.X0 + (size_t)cj.z * nx;
-                cgd dv = (cgd)v.dd + (size_t)cj.z * nu;
-                double s = 0.0;
+                const DynRow<T> f = row_f(cj.y, r);
+                cg<T> x = (cg<T>)z + p.X0 + (size_t)cj.z * nx;
+                cg<T> dv = (cg<T>)v.dd + (size_t)cj.z * nu;
+                T s = T(0);
                 for (int k = 0; k < nx; ++k) s = fma(f[k], x[k], s);
                 for (int k = 0; k < nu; ++k) s = fma(f[nx + k], dv[k], s);
                 z[p.X0 + (size_t)j * nx + r] = s;
@@ -334,27 +381,27 @@ __device__ __forceinline__ void dynamics_phase(const Dev& p, const View& v, glbd
 // Rows: per child j >= 1 eta3 (nx), eta4 (nu), eta5, eta6 (one SOC); per nonleaf i eta1
 // (2c + 1), eta2, eta7 (nx + nu, a box when the node has one); per leaf eta11 (nx), eta12,
 // eta13 (one SOC), eta14 (nx, a box when the leaf has one).
-template <int PASS, class PT>
-__device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, const View& v, double alpha, Maxima& mx,
+template <class T, int PASS, class PT>
+__device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, const View<T>& v, T alpha, Maxima<T>& mx,
                                            bool& nan, int tid, int nthr) {
     const int nx = p.nx, nu = p.nu;
-    cgd pz = v.pz, zp = v.zp, d = v.d;
+    cg<T> pz = v.pz, zp = v.zp, d = v.d;
     glbrec* frec = (glbrec*)p.frec;
     glbrec* crec = (glbrec*)p.crec;
     glbrec* lrec = (glbrec*)p.lrec;
-    auto put = [&](int e, double av, double bb, double shift) {
-        const double vv = (d[e] + alpha * av) / alpha + shift;
+    auto put = [&](int e, T av, T bb, T shift) {
+        const T vv = (d[e] + alpha * av) / alpha + shift;
         v.tv[e] = vv;
         v.xi2[e] = bb;
     };
-    auto finish = [&](int e, double vv, double pv) {
-        const double dv = d[e], bb = v.xi2[e];
-        const double ep = alpha * (vv - pv);
+    auto finish = [&](int e, T vv, T pv) {
+        const T dv = d[e], bb = v.xi2[e];
+        const T ep = alpha * (vv - pv);
         v.eo[e] = ep;
-        const double x2 = (dv - ep) / alpha + bb;
+        const T x2 = (dv - ep) / alpha + bb;
         v.xi2[e] = x2;
-        mx.m2 = nmax(mx.m2, fabs(x2));
-        mx.m5 = nmax(mx.m5, fabs(ep - dv));
+        mx.m2 = nmx<T>(mx.m2, fabs(x2));
+        mx.m5 = nmx<T>(mx.m5, fabs(ep - dv));
     };
     const int GC = nx + nu + 2;
     for (int it = tid; it < (p.n - 1) * GC; it += nthr) {
@@ -362,34 +409,34 @@ __device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, con
         const int e = r < nx ? e3(p, j) + r : (r < nx + nu ? e4(p, j) + r - nx : (r == nx + nu ? p.E5 : p.E6) + j);
         if (PASS == 1) {
             const Rec cr = crec[j];
-            double av, bb, shift = 0.0;
+            T av, bb, shift = T(0);
             if (r < nx + nu) {
                 const bool isx = r < nx;
                 const int rr = isx ? r : r - nx, len = isx ? nx : nu;
                 const PT M = isx ? tb.SQ + (size_t)cr.y * nx * nx + rr : tb.SR + (size_t)cr.z * nu * nu + rr;
                 const int o = isx ? p.X0 + cr.x * nx : p.U0 + cr.x * nu;
-                double sa = 0.0, sb = 0.0;
+                T sa = T(0), sb = T(0);
                 for (int k = 0; k < len; ++k) {
-                    const double mk = M[k * len], zk = zp[o + k], pk = pz[o + k];
-                    sa = fma(mk, 2.0 * zk - pk, sa);
+                    const T mk = M[k * len], zk = zp[o + k], pk = pz[o + k];
+                    sa = fma(mk, T(2) * zk - pk, sa);
                     sb = fma(mk, zk - pk, sb);
                 }
                 av = sa;
                 bb = sb;
             } else {
-                const double zt = zp[p.T0 + j], pt = pz[p.T0 + j];
-                av = 0.5 * (2.0 * zt - pt);
-                bb = 0.5 * (zt - pt);
-                shift = r == nx + nu ? -0.5 : 0.5;
+                const T zt = zp[p.T0 + j], pt = pz[p.T0 + j];
+                av = T(0.5) * (T(2) * zt - pt);
+                bb = T(0.5) * (zt - pt);
+                shift = r == nx + nu ? T(-0.5) : T(0.5);
             }
             put(e, av, bb, shift);
         } else {
-            double ss = 0.0;
+            T ss = T(0);
             const int o3 = e3(p, j), o4 = e4(p, j);
             for (int q = 0; q < nx; ++q) ss += v.tv[o3 + q] * v.tv[o3 + q];
             for (int q = 0; q < nu; ++q) ss += v.tv[o4 + q] * v.tv[o4 + q];
             ss += v.tv[p.E5 + j] * v.tv[p.E5 + j];
-            const double vv = v.tv[e];
+            const T vv = v.tv[e];
             finish(e, vv, soc_apply(vv, r == GC - 1, sqrt(ss), v.tv[p.E6 + j]));
         }
     }
@@ -401,39 +448,39 @@ __device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, con
         if (r < 2 * c + 1) {
             const int e = p.E1 + fr.x + r;
             if (PASS == 1) {
-                const double zy = zp[yo + r], py = pz[yo + r];
-                put(e, 2.0 * zy - py, zy - py, 0.0);
+                const T zy = zp[yo + r], py = pz[yo + r];
+                put(e, T(2) * zy - py, zy - py, T(0));
             } else {
-                const double vv = v.tv[e];
-                finish(e, vv, r < 2 * c ? fmax(vv, 0.0) : vv);
+                const T vv = v.tv[e];
+                finish(e, vv, r < 2 * c ? fmax(vv, T(0)) : vv);
             }
         } else if (r == 2 * p.cmax + 1) {
             const int e = p.E2 + i;
             if (PASS == 1) {
-                double bya = 0.0, byb = 0.0;
+                T bya = T(0), byb = T(0);
                 for (int k = 0; k < c; ++k) {
-                    const double cp = ((cgd)p.cond)[cs + k];
-                    bya = fma(cp, 2.0 * zp[yo + k] - pz[yo + k], bya);
+                    const T cp = ((cg<T>)p.cond)[cs + k];
+                    bya = fma(cp, T(2) * zp[yo + k] - pz[yo + k], bya);
                     byb = fma(cp, zp[yo + k] - pz[yo + k], byb);
                 }
-                bya += 2.0 * zp[yo + 2 * c] - pz[yo + 2 * c];
+                bya += T(2) * zp[yo + 2 * c] - pz[yo + 2 * c];
                 byb += zp[yo + 2 * c] - pz[yo + 2 * c];
-                const double zs = zp[p.S0 + i], ps = pz[p.S0 + i];
-                put(e, (2.0 * zs - ps) - bya, (zs - ps) - byb, 0.0);
+                const T zs = zp[p.S0 + i], ps = pz[p.S0 + i];
+                put(e, (T(2) * zs - ps) - bya, (zs - ps) - byb, T(0));
             } else {
-                const double vv = v.tv[e];
-                finish(e, vv, fmax(vv, 0.0));
+                const T vv = v.tv[e];
+                finish(e, vv, fmax(vv, T(0)));
             }
         } else if (r >= 2 * p.cmax + 2 && fr.w >= 0) {
             const int rr = r - (2 * p.cmax + 2);
             const int e = fr.w + rr;
             if (PASS == 1) {
                 const int o = rr < nx ? p.X0 + i * nx + rr : p.U0 + i * nu + rr - nx;
-                const double zv = zp[o], pv = pz[o];
-                put(e, 2.0 * zv - pv, zv - pv, 0.0);
+                const T zv = zp[o], pv = pz[o];
+                put(e, T(2) * zv - pv, zv - pv, T(0));
             } else {
                 const int bi = ((glbi*)p.iBnl)[i];
-                const double vv = v.tv[e];
+                const T vv = v.tv[e];
                 finish(e, vv, box_apply(vv, tb.BLn[(size_t)bi * (nx + nu) + rr], tb.BHn[(size_t)bi * (nx + nu) + rr], nan));
             }
         }
@@ -445,110 +492,114 @@ __device__ __forceinline__ void dual_phase(const Dev& p, const Tabs<PT>& tb, con
         if (r < nx + 2) {
             const int e = r < nx ? e11(p, l) + r : (r == nx ? p.E12 : p.E13) + l;
             if (PASS == 1) {
-                double av, bb, shift = 0.0;
+                T av, bb, shift = T(0);
                 if (r < nx) {
                     const PT M = tb.SP + (size_t)lr.x * nx * nx + r;
                     const int o = p.X0 + l * nx;
-                    double sa = 0.0, sb = 0.0;
+                    T sa = T(0), sb = T(0);
                     for (int k = 0; k < nx; ++k) {
-                        const double mk = M[k * nx], zk = zp[o + k], pk = pz[o + k];
-                        sa = fma(mk, 2.0 * zk - pk, sa);
+                        const T mk = M[k * nx], zk = zp[o + k], pk = pz[o + k];
+                        sa = fma(mk, T(2) * zk - pk, sa);
                         sb = fma(mk, zk - pk, sb);
                     }
                     av = sa;
                     bb = sb;
                 } else {
-                    const double zs = zp[p.S0 + l], ps = pz[p.S0 + l];
-                    av = 0.5 * (2.0 * zs - ps);
-                    bb = 0.5 * (zs - ps);
-                    shift = r == nx ? -0.5 : 0.5;
+                    const T zs = zp[p.S0 + l], ps = pz[p.S0 + l];
+                    av = T(0.5) * (T(2) * zs - ps);
+                    bb = T(0.5) * (zs - ps);
+                    shift = r == nx ? T(-0.5) : T(0.5);
                 }
                 put(e, av, bb, shift);
             } else {
-                double ss = 0.0;
+                T ss = T(0);
                 const int o11 = e11(p, l);
                 for (int q = 0; q < nx; ++q) ss += v.tv[o11 + q] * v.tv[o11 + q];
                 ss += v.tv[p.E12 + l] * v.tv[p.E12 + l];
-                const double vv = v.tv[e];
+                const T vv = v.tv[e];
                 finish(e, vv, soc_apply(vv, r == nx + 1, sqrt(ss), v.tv[p.E13 + l]));
             }
         } else if (lr.z >= 0) {
             const int rr = r - nx - 2;
             const int e = lr.z + rr;
             if (PASS == 1) {
-                const double zv = zp[p.X0 + l * nx + rr], pv = pz[p.X0 + l * nx + rr];
-                put(e, 2.0 * zv - pv, zv - pv, 0.0);
+                const T zv = zp[p.X0 + l * nx + rr], pv = pz[p.X0 + l * nx + rr];
+                put(e, T(2) * zv - pv, zv - pv, T(0));
             } else {
-                const double vv = v.tv[e];
+                const T vv = v.tv[e];
                 finish(e, vv, box_apply(vv, tb.BLl[(size_t)lr.y * nx + rr], tb.BHl[(size_t)lr.y * nx + rr], nan));
             }
         }
     }
 }
 
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_xor(v, off, 64));
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+    for (int off = 32; off > 0; off >>= 1) v = nmx<T>(v, __shfl_xor(v, off, 64));
     return v;
 }
 
-__device__ __forceinline__ View view_of(double* slab, const CpbSlab& L, int k) {
-    View v;
-    v.pz = (glbd*)(slab + L.z[k % 3]);
-    v.zp = (glbd*)(slab + L.z[(k + 1) % 3]);
-    v.out = (glbd*)(slab + L.z[(k + 2) % 3]);
-    v.d = (glbd*)(slab + L.e[k % 2]);
-    v.eo = (glbd*)(slab + L.e[(k + 1) % 2]);
-    v.xi2 = (glbd*)(slab + L.xi2);
-    v.tv = (glbd*)(slab + L.tv);
-    v.q = (glbd*)(slab + L.q);
-    v.dd = (glbd*)(slab + L.dd);
-    v.pb = (glbd*)(slab + L.pb);
-    v.x0 = (cgd)(slab + L.x0);
+template <class T>
+__device__ __forceinline__ View<T> view_of(T* slab, const CpbSlab& L, int k) {
+    View<T> v;
+    v.pz = (gl<T>*)(slab + L.z[k % 3]);
+    v.zp = (gl<T>*)(slab + L.z[(k + 1) % 3]);
+    v.out = (gl<T>*)(slab + L.z[(k + 2) % 3]);
+    v.d = (gl<T>*)(slab + L.e[k % 2]);
+    v.eo = (gl<T>*)(slab + L.e[(k + 1) % 2]);
+    v.xi2 = (gl<T>*)(slab + L.xi2);
+    v.tv = (gl<T>*)(slab + L.tv);
+    v.q = (gl<T>*)(slab + L.q);
+    v.dd = (gl<T>*)(slab + L.dd);
+    v.pb = (gl<T>*)(slab + L.pb);
+    v.x0 = (cg<T>)(slab + L.x0);
     return v;
 }
 
-template <class PT>
+// The residual maxima are taken in T; the history row is their widening to double (exact) and
+// the stopping test compares in double, as cp_check_wave does on an fp32 context.
+template <class T, class PT>
 __device__ __forceinline__ void cpb_body(const Dev& p, const CpbArg& a, const Tabs<PT>& tb, int b) {
-    __shared__ double s_red[6][kCpbBlock / 64];
+    __shared__ T s_red[6][kCpbBlock / 64];
     __shared__ int s_ctl[2];  // {done, k} of the instance, as thread 0 left them
     const int tid = threadIdx.x, nthr = blockDim.x;
     Ctl* ctl = a.ctl + b;
-    double* slab = a.slab + (size_t)b * a.lay.stride;
+    T* slab = (T*)a.slab + (size_t)b * a.lay.stride;
     double* hist = a.hist + (size_t)b * a.hist_rows * 6;
-    const double alpha = ctl->alpha;
+    const T alpha = (T)ctl->alpha;
     int k = ctl->k;
     if (!ctl->pad) {
         // the solve's first half step Z[1] = prox-part(Z[0] - alpha L^T E[0])
-        const View v = view_of(slab, a.lay, 0);
-        Maxima none;
-        primal_phase<false>(p, tb, v, v.zp, alpha, none, tid, nthr);
+        const View<T> v = view_of(slab, a.lay, 0);
+        Maxima<T> none;
+        primal_phase<T, false>(p, tb, v, v.zp, alpha, none, tid, nthr);
         __syncthreads();
         if (tid == 0) ctl->pad = 1;
     }
     for (int it = 0; it < a.chunk; ++it) {
-        const View v = view_of(slab, a.lay, k);
-        Maxima mx;
+        const View<T> v = view_of(slab, a.lay, k);
+        Maxima<T> mx;
         bool nan = false;
-        dynamics_phase(p, v, v.zp, tid, nthr);
-        dual_phase<1>(p, tb, v, alpha, mx, nan, tid, nthr);
+        dynamics_phase<T>(p, a, v, v.zp, tid, nthr);
+        dual_phase<T, 1>(p, tb, v, alpha, mx, nan, tid, nthr);
         __syncthreads();
-        dual_phase<2>(p, tb, v, alpha, mx, nan, tid, nthr);
+        dual_phase<T, 2>(p, tb, v, alpha, mx, nan, tid, nthr);
         __syncthreads();
-        primal_phase<true>(p, tb, v, v.out, alpha, mx, tid, nthr);
+        primal_phase<T, true>(p, tb, v, v.out, alpha, mx, tid, nthr);
         // the six maxima of the instance, its history row and the stopping test (cp_check_wave)
-        const double mm[6] = {wave_max(mx.m0), wave_max(mx.m1), wave_max(mx.m2),
+        const T mm[6] = {wave_max(mx.m0), wave_max(mx.m1), wave_max(mx.m2),
                               wave_max(mx.m3), wave_max(mx.m4), wave_max(mx.m5)};
         if ((tid & 63) == 0) _Pragma("unroll") for (int q = 0; q < 6; ++q) s_red[q][tid >> 6] = mm[q];
         const int any_nan = __syncthreads_or(nan ? 1 : 0);
         if (tid == 0) {
-            double m[6];
+            T m[6];
             _Pragma("unroll") for (int q = 0; q < 6; ++q) {
-                double r = s_red[q][0];
-                for (int w = 1; w < (nthr >> 6); ++w) r = nmax(r, s_red[q][w]);
+                T r = s_red[q][0];
+                for (int w = 1; w < (nthr >> 6); ++w) r = nmx<T>(r, s_red[q][w]);
                 m[q] = r;
-                hist[(size_t)k * 6 + q] = r;
+                hist[(size_t)k * 6 + q] = (double)r;
             }
-            const double err = nmax(nmax(m[0], m[1]), m[2]);
+            const double err = (double)nmx<T>(nmx<T>(m[0], m[1]), m[2]);
             int done = 0;
             if (any_nan) ctl->flags |= 1;
             if (k >= ctl->max_iters || err <= ctl->tol || any_nan) {
@@ -566,22 +617,22 @@ __device__ __forceinline__ void cpb_body(const Dev& p, const CpbArg& a, const Ta
         const int done = s_ctl[0];
         k = s_ctl[1];
         if (done) {
-            if (tid < p.nu) a.u0[(size_t)b * p.nu + tid] = v.zp[p.U0 + tid];
+            if (tid < p.nu) a.u0[(size_t)b * p.nu + tid] = (double)v.zp[p.U0 + tid];
             break;
         }
     }
 }
 
-template <bool LT>
+template <class T, bool LT>
 __global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
-    extern __shared__ __attribute__((aligned(16))) double smem_[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_[];
     const int b = blockIdx.x;
     if (b >= a.B || a.ctl[b].done) return;  // a finished instance leaves at kernel entry
     const int nx = p.nx, nu = p.nu;
     const int nQ = p.nSQ * nx * nx, nR = p.nSR * nu * nu, nP = p.nSP * nx * nx, nBn = p.nBnl * (nx + nu), nBl = p.nBl * nx;
     if constexpr (LT) {
-        ldsd* s = (ldsd*)smem_;
-        const cgd src[7] = {(cgd)p.SQ, (cgd)p.SR, (cgd)p.SP, (cgd)p.blo_nl, (cgd)p.bhi_nl, (cgd)p.blo_l, (cgd)p.bhi_l};
+        __attribute__((address_space(3))) T* s = (__attribute__((address_space(3))) T*)smem_;
+        const cg<T> src[7] = {(cg<T>)p.SQ, (cg<T>)p.SR, (cg<T>)p.SP, (cg<T>)p.blo_nl, (cg<T>)p.bhi_nl, (cg<T>)p.blo_l, (cg<T>)p.bhi_l};
         const int cnt[7] = {nQ, nR, nP, nBn, nBn, nBl, nBl};
         int off[8];
         off[0] = 0;
@@ -589,11 +640,11 @@ __global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
         _Pragma("unroll") for (int t = 0; t < 7; ++t)
             for (int e = threadIdx.x; e < cnt[t]; e += blockDim.x) s[off[t] + e] = src[t][e];
         __syncthreads();
-        const Tabs<cld> tb{s + off[0], s + off[1], s + off[2], s + off[3], s + off[4], s + off[5], s + off[6]};
-        cpb_body(p, a, tb, b);
+        const Tabs<cl<T>> tb{s + off[0], s + off[1], s + off[2], s + off[3], s + off[4], s + off[5], s + off[6]};
+        cpb_body<T>(p, a, tb, b);
     } else {
-        const Tabs<cgd> tb{(cgd)p.SQ, (cgd)p.SR, (cgd)p.SP, (cgd)p.blo_nl, (cgd)p.bhi_nl, (cgd)p.blo_l, (cgd)p.bhi_l};
-        cpb_body(p, a, tb, b);
+        const Tabs<cg<T>> tb{(cg<T>)p.SQ, (cg<T>)p.SR, (cg<T>)p.SP, (cg<T>)p.blo_nl, (cg<T>)p.bhi_nl, (cg<T>)p.blo_l, (cg<T>)p.bhi_l};
+        cpb_body<T>(p, a, tb, b);
     }
 }
 
@@ -610,26 +661,30 @@ __global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
 //      Z[0] and to the slab's x0, and the instance's Ctl and done word are reset.
 // An instance whose solve raised the NaN flag is frozen: its slab, Ctl and done word stay, this
 // step and every later one record status 2 (later ones: 0 iterations) and NaN for x+, u, l.
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) d2 glbd2;
-
+// The plant step and the stage cost are computed in T; the records X, U, cost and err are double
+// for either T (widened at the store), status and iters int.
+template <class T>
 __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg m) {
-    __shared__ double s_x[kCpbMaxNx], s_u[kCpbMaxNu], s_xp[kCpbMaxNx], s_sq[kCpbMaxNx + kCpbMaxNu];
+    // 16 bytes of the slab: 2 doubles or 4 floats
+    constexpr int VN = 16 / (int)sizeof(T);
+    typedef T vt __attribute__((ext_vector_type(VN)));
+    typedef __attribute__((address_space(1))) vt glbvt;
+    __shared__ T s_x[kCpbMaxNx], s_u[kCpbMaxNu], s_xp[kCpbMaxNx], s_sq[kCpbMaxNx + kCpbMaxNu];
     const int b = blockIdx.x;
     if (b >= a.B) return;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    const int nx = p.nx, nu = p.nu, T = m.T, t = m.t;
+    const int nx = p.nx, nu = p.nu, NT = m.T, t = m.t;
     Ctl* ctl = a.ctl + b;
-    double* slab = a.slab + (size_t)b * a.lay.stride;
-    glbd* Xo = (glbd*)(m.X + ((size_t)b * (T + 1) + t) * nx);
-    glbd* Uo = (glbd*)(m.U + ((size_t)b * T + t) * nu);
-    const size_t bt = (size_t)b * T + t;
+    T* slab = (T*)a.slab + (size_t)b * a.lay.stride;
+    gl<double>* Xo = (gl<double>*)(m.X + ((size_t)b * (NT + 1) + t) * nx);
+    gl<double>* Uo = (gl<double>*)(m.U + ((size_t)b * NT + t) * nu);
+    const size_t bt = (size_t)b * NT + t;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     // uniform over the workgroup: nobody writes these words before the barrier below
     const int fk = ctl->final_k, flags = ctl->flags, max_iters = ctl->max_iters;
     const int frz = m.frz[b];
-    cgd x = (cgd)(slab + a.lay.x0);
-    if (t == 0 && tid < nx) Xo[tid] = x[tid];
+    cg<T> x = (cg<T>)(slab + a.lay.x0);
+    if (t == 0 && tid < nx) Xo[tid] = (double)x[tid];
     if (frz >= 0 || (flags & 1)) {
         if (tid < nx) Xo[nx + tid] = qnan;
         if (tid < nu) Uo[tid] = qnan;
@@ -644,7 +699,7 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
         return;
     }
     const int zs = (fk + 1) % 3, es = (fk + 1) % 2;
-    cgd zf = (cgd)(slab + a.lay.z[zs]);
+    cg<T> zf = (cg<T>)(slab + a.lay.z[zs]);
     if (tid < nx) s_x[tid] = x[tid];
     if (tid < nu) s_u[tid] = zf[p.U0 + tid];
     __syncthreads();
@@ -652,44 +707,45 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
     const int i = ((glbi*)p.ch_start)[0] + j;
     const Rec cr = ((glbrec*)p.crec)[i];
     if (tid < nx) {
-        cgd Ar = (cgd)m.ab + ((size_t)j * (nx + nu) + tid) * nx;
-        cgd Br = (cgd)m.ab + ((size_t)j * (nx + nu) + nx) * nx + (size_t)tid * nu;
-        double s = 0.0;
+        cg<T> Ar = (cg<T>)m.ab + ((size_t)j * (nx + nu) + tid) * nx;
+        cg<T> Br = (cg<T>)m.ab + ((size_t)j * (nx + nu) + nx) * nx + (size_t)tid * nu;
+        T s = T(0);
         for (int k = 0; k < nx; ++k) s = fma(Ar[k], s_x[k], s);
         for (int k = 0; k < nu; ++k) s = fma(Br[k], s_u[k], s);
         s_xp[tid] = s;
-        Xo[nx + tid] = s;
+        Xo[nx + tid] = (double)s;
     } else if (tid >= 64 && tid < 64 + nx + nu) {
         // the column-major L weights: M[k * rows + r] = M_rk
         const int r = tid - 64;
         const bool isx = r < nx;
         const int rr = isx ? r : r - nx, len = isx ? nx : nu;
-        cgd M = isx ? (cgd)p.SQ + (size_t)cr.y * nx * nx + rr : (cgd)p.SR + (size_t)cr.z * nu * nu + rr;
-        const double* v = isx ? s_x : s_u;
-        double s = 0.0;
+        cg<T> M = isx ? (cg<T>)p.SQ + (size_t)cr.y * nx * nx + rr : (cg<T>)p.SR + (size_t)cr.z * nu * nu + rr;
+        const T* v = isx ? s_x : s_u;
+        T s = T(0);
         for (int k = 0; k < len; ++k) s = fma(M[k * len], v[k], s);
         s_sq[r] = s * s;
     }
-    if (tid < nu) Uo[tid] = s_u[tid];
+    if (tid < nu) Uo[tid] = (double)s_u[tid];
     if (tid < 3) m.err[bt * 3 + tid] = a.hist[((size_t)b * a.hist_rows + fk) * 6 + tid];
     __syncthreads();
     if (tid == 0) {
-        double l = 0.0;
+        T l = T(0);
         for (int r = 0; r < nx + nu; ++r) l += s_sq[r];
-        m.cost[bt] = l;
+        m.cost[bt] = (double)l;
         m.status[bt] = fk < max_iters ? 0 : 1;
         m.iters[bt] = fk + 1;
     }
     if (m.last) return;
-    // every array of the slab starts on a 16-B boundary and has an even length in the layout
-    // (cpb_layout: Z[0] at the slab's start, then Z[1], Z[2], E[0], E[1] and the work arrays)
+    // every array of the slab starts on a 16-B boundary and its length in the layout is a whole
+    // number of 16-B vectors, the stride a multiple of 256 B (cpb_layout_dims: Z[0] at the slab's
+    // start, then Z[1], Z[2], E[0], E[1] and the work arrays)
     const CpbSlab& L = a.lay;
-    glbd2* s2 = (glbd2*)slab;
-    const d2 zero = {0.0, 0.0};
-    const long z1 = L.z[1] / 2, e0 = L.e[0] / 2, e1 = L.e[1] / 2, end = L.stride / 2;
+    glbvt* s2 = (glbvt*)slab;
+    const vt zero = T(0);
+    const long z1 = L.z[1] / VN, e0 = L.e[0] / VN, e1 = L.e[1] / VN, end = L.stride / VN;
     if (m.warm) {
         if (zs != 0) {
-            const long src = L.z[zs] / 2;
+            const long src = L.z[zs] / VN;
             for (long q = tid; q < z1; q += nthr) s2[q] = s2[src + q];
         }
         if (es != 0)
@@ -702,9 +758,9 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
     }
     __syncthreads();  // x+ lands in ranges other lanes have just written
     if (tid < nx) {
-        const double v = s_xp[tid];
-        ((glbd*)slab)[L.z[0] + p.X0 + tid] = v;
-        ((glbd*)slab)[L.x0 + tid] = v;
+        const T v = s_xp[tid];
+        ((gl<T>*)slab)[L.z[0] + p.X0 + tid] = v;
+        ((gl<T>*)slab)[L.x0 + tid] = v;
     }
     if (tid == 0) {
         _Pragma("unroll") for (int q = 0; q < 6; ++q) ctl->red[q] = 0;
@@ -717,53 +773,49 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
     }
 }
 
-long tab_doubles(const Dev& p) {
+// elements of the shared tables (sqrt Q, sqrt R, sqrt Pf and the four box tables)
+long tab_elems(const Dev& p) {
     return (long)p.nSQ * p.nx * p.nx + (long)p.nSR * p.nu * p.nu + (long)p.nSP * p.nx * p.nx +
            2L * p.nBnl * (p.nx + p.nu) + 2L * p.nBl * p.nx;
 }
 
-}  // namespace
-
-CpbSlab cpb_layout(const Dev& p) {
-    CpbSlab L{};
-    long at = 0;
-    auto take = [&](long count) {
-        const long o = at;
-        at += (count + 1) / 2 * 2;
-        return o;
-    };
-    for (int b = 0; b < 3; ++b) L.z[b] = take(p.P);
-    for (int b = 0; b < 2; ++b) L.e[b] = take(p.D);
-    L.xi2 = take(p.D);
-    L.tv = take(p.D);
-    L.q = take((long)p.n * p.nx);
-    L.dd = take((long)p.m * p.nu);
-    L.pb = take((long)p.n * (p.nx + p.nu));
-    L.x0 = take(p.nx);
-    L.stride = (at + 31) / 32 * 32;
-    return L;
+template <class T>
+hipError_t cpb_launch_t(const Dev& p, const CpbArg& a, hipStream_t stream) {
+    if (a.lds_tabs)
+        k_cpb<T, true><<<a.B, kCpbBlock, tab_elems(p) * sizeof(T), stream>>>(p, a);
+    else
+        k_cpb<T, false><<<a.B, kCpbBlock, 0, stream>>>(p, a);
+    return hipGetLastError();
 }
 
-size_t cpb_tab_bytes(const Dev& p) {
-    const long b = tab_doubles(p) * (long)sizeof(double);
+}  // namespace
+
+CpbSlab cpb_layout(const Dev& p, bool f32) {
+    return cpb_layout_dims(p.P, p.D, p.n, p.m, p.nx, p.nu, f32 ? (int)sizeof(float) : (int)sizeof(double));
+}
+
+size_t cpb_tab_bytes(const Dev& p, bool f32) {
+    const long b = tab_elems(p) * (long)(f32 ? sizeof(float) : sizeof(double));
     return b <= kCpbLdsTabs ? (size_t)b : 0;
 }
 
-hipError_t cpb_launch(const Dev& p, const CpbArg& a, hipStream_t stream) {
-    if (a.lds_tabs)
-        k_cpb<true><<<a.B, kCpbBlock, tab_doubles(p) * sizeof(double), stream>>>(p, a);
+hipError_t cpb_launch(const Dev& p, const CpbArg& a, bool f32, hipStream_t stream) {
+    return f32 ? cpb_launch_t<float>(p, a, stream) : cpb_launch_t<double>(p, a, stream);
+}
+
+const char* cpb_name(bool f32, bool lds_tabs) {
+    if (f32) return lds_tabs ? "k_cpb<float, true>" : "k_cpb<float, false>";
+    return lds_tabs ? "k_cpb<true>" : "k_cpb<false>";
+}
+
+hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, bool f32, hipStream_t stream) {
+    if (f32)
+        k_mpc_step<float><<<a.B, kCpbBlock, 0, stream>>>(p, a, m);
     else
-        k_cpb<false><<<a.B, kCpbBlock, 0, stream>>>(p, a);
+        k_mpc_step<double><<<a.B, kCpbBlock, 0, stream>>>(p, a, m);
     return hipGetLastError();
 }
 
-const char* cpb_name(bool lds_tabs) { return lds_tabs ? "k_cpb<true>" : "k_cpb<false>"; }
-
-hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, hipStream_t stream) {
-    k_mpc_step<<<a.B, kCpbBlock, 0, stream>>>(p, a, m);
-    return hipGetLastError();
-}
-
-const char* mpc_step_name() { return "k_mpc_step"; }
+const char* mpc_step_name(bool f32) { return f32 ? "k_mpc_step<float>" : "k_mpc_step"; }
 
 }  // namespace raocp

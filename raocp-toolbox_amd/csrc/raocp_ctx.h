@@ -205,7 +205,7 @@ struct raocp_ctx {
         int cap_B = 0;               // instances the device buffers hold
         size_t hist_rows = 0;
         raocp::CpbSlab lay{};
-        double* slab = nullptr;
+        char* slab = nullptr;        // elements of the context's scalar type (wsz bytes each)
         Ctl* ctl = nullptr;
         int* done = nullptr;
         double* hist = nullptr;
@@ -214,7 +214,8 @@ struct raocp_ctx {
         std::vector<double> hz, he, hu0;  // the sequential solves' final iterates and first inputs
     } bt;
     // closed-loop simulation of a batch (raocp_cp_batch_mpc): the plant tables of the root's
-    // children (host copies from create; A | B uploaded at the first simulation) and the
+    // children (host copies from create; A | B uploaded at the first simulation in the
+    // context's scalar type) and the
     // device block of the per-step records, reused while it is large enough
     std::vector<double> h_mpc_ab, h_mpc_w;
     const double* d_mpc_ab = nullptr;

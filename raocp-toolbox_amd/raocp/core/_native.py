@@ -366,8 +366,9 @@ class NativeContext:
                 [derr[b, :iters[b]].copy() for b in range(B)])
 
     def cp_batch_get(self, b):
-        """(z, eta) of instance b of the last batch, in the reference's flat order."""
-        z, e = np.empty(self.P), np.empty(self.D)
+        """(z, eta) of instance b of the last batch, in the reference's flat order: float64 arrays
+        on either context (an fp32 context widens its slab's floats, as get_primal does)."""
+        z, e = np.empty(self.P, dtype=np.float64), np.empty(self.D, dtype=np.float64)
         self._check(self._lib.raocp_cp_batch_get(self._h, int(b), _ptr(z), _ptr(e)))
         return z, e
 

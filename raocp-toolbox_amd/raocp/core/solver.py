@@ -180,7 +180,10 @@ class Solver:
         warm=True continues every instance from the iterate the previous chock_batch left (the
         batch size must be the same). Results: batch_error_cache[b], batch_delta_error_cache[b],
         batch_primal_flat(b), batch_dual_flat(b), batch_first_inputs(). If a NaN reached a box
-        projection in some instances, the results are stored and ValueError names them."""
+        projection in some instances, the results are stored and ValueError names them.
+        A float32 solver returns the same types, shapes and dtypes; it runs the batch kernel's
+        float form when the environment has RAOCP_CPB_F32=1 and the solves one after another
+        otherwise (the same holds for simulate_batch)."""
         nx = self.__raocp.state_dynamics_at_node(1).shape[1]
         x0 = normalise_initial_states(initial_states, nx)
         B = x0.shape[0]

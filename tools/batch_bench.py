@@ -34,20 +34,24 @@ def main():
     ap.add_argument("--B", default="1,16,256,1024")
     ap.add_argument("--K", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.dtype == "float32":
+        # the float batch kernel is opt-in; RAOCP_CPB=0 still selects the sequential fallback
+        os.environ.setdefault("RAOCP_CPB_F32", "1")
     import raocp.core as core
     from raocp.core._native import device_synchronize
     from raocp.problems import build_problem, recipe_main
 
     r = recipe_main()
     tree, prob = build_problem(r)
-    cache = core.Cache(prob, device=0)
+    cache = core.Cache(prob, device=0, dtype=a.dtype)
     nat = cache.native
     alpha = 0.999 / nat.step_size()
     x0 = np.asarray(r["x0"], dtype=float).reshape(-1)
     K = a.K
-    res = {"problem": "main.py (43 nodes, nx 3, nu 2)", "K": K, "alpha": alpha, "reps": a.reps, "legs": {}}
+    res = {"problem": "main.py (43 nodes, nx 3, nu 2)", "dtype": a.dtype, "K": K, "alpha": alpha, "reps": a.reps, "legs": {}}
 
     def timed(fn):
         fn()  # warm-up, discarded

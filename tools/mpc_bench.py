@@ -37,8 +37,12 @@ def main():
     ap.add_argument("--T", type=int, default=20)
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.dtype == "float32":
+        # the float kernels are opt-in; RAOCP_CPB=0 still selects the host loop over sequential solves
+        os.environ.setdefault("RAOCP_CPB_F32", "1")
     import raocp.core as core
     from raocp.core._native import device_synchronize
     from raocp.core.solver import sample_scenarios
@@ -46,7 +50,7 @@ def main():
 
     r = recipe_main()
     tree, prob = build_problem(r)
-    cache = core.Cache(prob, device=0)
+    cache = core.Cache(prob, device=0, dtype=a.dtype)
     nat = cache.native
     alpha = 0.999 / nat.step_size()
     x0 = np.asarray(r["x0"], dtype=float).reshape(-1)
@@ -54,7 +58,7 @@ def main():
     children = [int(i) for i in tree.children_of(0)]
     A = np.stack([np.asarray(prob.state_dynamics_at_node(i), dtype=float) for i in children])
     Bm = np.stack([np.asarray(prob.control_dynamics_at_node(i), dtype=float) for i in children])
-    res = {"problem": "main.py (43 nodes, nx 3, nu 2)", "T": T, "K": K, "alpha": alpha, "reps": a.reps, "legs": {}}
+    res = {"problem": "main.py (43 nodes, nx 3, nu 2)", "dtype": a.dtype, "T": T, "K": K, "alpha": alpha, "reps": a.reps, "legs": {}}
 
     def timed(fn):
         fn()  # warm-up, discarded
