@@ -503,6 +503,99 @@ class OracleProblem:
             raise ValueError(f"Rectangle constraint - '{bad}' value cannot be constrained")
         return np.where(v <= lo, lo, np.where(v >= hi, hi, v))
 
+    # ------------------------------------------------------------------------------------------
+    # which slots are live, and which branch of the projections a modified dual takes (census)
+    # ------------------------------------------------------------------------------------------
+    def live_masks(self):
+        """(primal mask, dual mask) over the flat vectors: True on the slots some operator or
+        projection writes, False on the (1,1) zero placeholders (tau_0; eta1, eta2 of leaves;
+        eta3..eta6 of node 0; eta7 / eta14 of unboxed nodes; eta11..eta14 of nonleaf nodes)."""
+        n, m, nx, nu = self.n, self.m, self.nx, self.nu
+        pm = np.ones(self.P, dtype=bool)
+        pm[self.T0] = False
+        dm = np.zeros(self.D, dtype=bool)
+        dm[self.e1_all] = True
+        dm[self.E2[:m]] = True
+        j, lf = self.kids, self.leaves
+        dm[(self.E3[j][:, None] + np.arange(nx)).reshape(-1)] = True
+        dm[(self.E4[j][:, None] + np.arange(nu)).reshape(-1)] = True
+        dm[self.E5[j]] = True
+        dm[self.E6[j]] = True
+        act = np.flatnonzero(self.nl_active)
+        if act.size:
+            dm[(self.E7[act][:, None] + np.arange(nx + nu)).reshape(-1)] = True
+        dm[(self.E11[lf][:, None] + np.arange(nx)).reshape(-1)] = True
+        dm[self.E12[lf]] = True
+        dm[self.E13[lf]] = True
+        lact = np.flatnonzero(self.l_active)
+        if lact.size:
+            dm[(self.E14[lf[lact]][:, None] + np.arange(nx)).reshape(-1)] = True
+        return pm, dm
+
+    SOC_CLASSES = ("identity", "zero", "scaling")
+
+    @staticmethod
+    def _soc_class(F, t):
+        """Per row of [F | t]: the branch _soc takes (0 identity, 1 zero, 2 scaling, by the same
+        comparisons in the same order) and the margin |nf - |t|| / max(nf, |t|) of that choice."""
+        nf = np.linalg.norm(F, axis=1)
+        cls = np.where(nf <= t, 0, np.where(nf <= -t, 1, 2))
+        big = np.maximum(nf, np.abs(t))
+        margin = np.abs(nf - np.abs(t)) / np.where(big > 0, big, 1.0)
+        return cls, margin
+
+    def branch_census(self, v):
+        """The branches project_on_constraints_nonleaf / _leaf take on the modified dual v (after
+        modify_dual_add_halves). Returns a dict:
+          child_class, child_margin   per child cone, in the order of self.kids (nodes 1..n-1)
+          leaf_class, leaf_margin     per leaf cone, in the order of self.leaves
+          box_nl, box_l               [lo, hi, inside] counts of the eta7 / eta14 entries
+          eta1_sign, eta2_sign        [positive, negative] counts of the entries under max(0, .)
+        Entries exactly at a bound count with that bound, as _clip resolves them; a clamped entry
+        that is exactly zero counts with neither sign."""
+        nx, nu, m = self.nx, self.nu, self.m
+        v = np.asarray(v, dtype=float)
+        j, lf = self.kids, self.leaves
+        F = np.concatenate([v[self.E3[j][:, None] + np.arange(nx)], v[self.E4[j][:, None] + np.arange(nu)],
+                            v[self.E5[j]][:, None]], axis=1)
+        ccls, cmar = self._soc_class(F, v[self.E6[j]])
+        Fl = np.concatenate([v[self.E11[lf][:, None] + np.arange(nx)], v[self.E12[lf]][:, None]], axis=1)
+        lcls, lmar = self._soc_class(Fl, v[self.E13[lf]])
+
+        def box(w, lo, hi):
+            return np.array([int((w <= lo).sum()), int(((w > lo) & (w >= hi)).sum()), int(((w > lo) & (w < hi)).sum())])
+
+        act = np.flatnonzero(self.nl_active)
+        lact = np.flatnonzero(self.l_active)
+        bnl = box(v[self.E7[act][:, None] + np.arange(nx + nu)], self.nl_lo[act], self.nl_hi[act]) if act.size \
+            else np.zeros(3, dtype=np.int64)
+        bl = box(v[self.E14[lf[lact]][:, None] + np.arange(nx)], self.l_lo[lact], self.l_hi[lact]) if lact.size \
+            else np.zeros(3, dtype=np.int64)
+        mask_last = np.zeros(self.y_all.size, dtype=bool)
+        mask_last[_offsets(2 * self.nch + 1)[1:] - 1] = True
+        e1 = v[self.e1_all][~mask_last]
+        e2 = v[self.E2[:m]]
+        return dict(child_class=ccls, child_margin=cmar, leaf_class=lcls, leaf_margin=lmar, box_nl=bnl, box_l=bl,
+                    eta1_sign=np.array([int((e1 > 0).sum()), int((e1 < 0).sum())]),
+                    eta2_sign=np.array([int((e2 > 0).sum()), int((e2 < 0).sum())]))
+
+    def chock_modified_duals(self, x0, max_iters, alpha, p0=None, d0=None):
+        """The modified dual v (the argument of the projections) of every iteration of
+        chock(x0, max_iters, 0.0, alpha, p0, d0): a list of max_iters + 1 flat duals, the first
+        one iteration 1's. For branch_census; chock itself is untouched."""
+        p = self.initial_primal(x0)
+        if p0 is not None:
+            p = np.array(p0, dtype=float, copy=True)
+            p[self.X0:self.X0 + self.nx] = np.asarray(x0, dtype=float).reshape(-1)
+        d = np.zeros(self.D) if d0 is None else np.array(d0, dtype=float, copy=True)
+        out = []
+        for _ in range(int(max_iters) + 1):
+            zp = self.prox_f(p - alpha * self.ell_t(d, template=p), alpha, x0)
+            eh = d + alpha * self.ell(2 * zp - p, template=d)
+            out.append(self.modify_dual_add_halves(eh, alpha))
+            p, d = zp, self.prox_gconj(eh, alpha)
+        return out
+
     def prox_gconj(self, eta, alpha):
         """cache.py:321-327 and 392-393: Moreau, eta+ = alpha (v - Pi(v))."""
         v = self.modify_dual_add_halves(eta, alpha)

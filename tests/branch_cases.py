@@ -1,0 +1,285 @@
+"""The trees and crafted warm starts shared by tests/test_branch_census.py (CPU: the oracle's
+census of every start) and tests/test_gpu_branches.py (GPU: every CP kernel family on them).
+
+A cold-started CP trajectory on the suite's trees stays in the scaling branch of the
+second-order-cone projection and almost wholly inside the boxes ("Branch coverage of
+the dual step"), so these starts are built to take every branch in their first iteration
+(helpers.crafted_start) and the census test proves that they do.
+"""
+import functools
+import os
+
+import numpy as np
+
+from raocp.problems import build_problem, recipe_from_npz, recipe_synthetic
+from helpers import crafted_rotations, crafted_start
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_FILE = {"main": "main_trace", "bin6": "traj_small", "c1n5": "traj_small"}
+# Seeds of the crafted starts: the smallest for which the start meets every census condition
+# (census_violations; tests/test_branch_census.py asserts them for every start used). The
+# synthetic trees all take 1; the small cones of main (nx = 3) and c1n5 (nx = 4) leave a cone
+# kept at its random value near an edge more often, so fewer seeds qualify there.
+SEED = 1
+SEEDS = {"main": 32, "c1n5": 5}
+# one start per instance of a batch
+BATCH_SEEDS = {"main": (32, 37, 50), "bin6": (1, 2, 3), "c1n5": (5, 12, 46), "m7x32": (1, 2, 3)}
+# the form of the batch kernel each problem reaches (kernel_info(13)), fp64 / fp32: the tables of the
+# golden problems fit the kernel's LDS budget and are staged there, those of m7x32 are read from HBM
+BATCH_KERNEL = {"main": ("k_cpb<true>", "k_cpb<float, true>"), "bin6": ("k_cpb<true>", "k_cpb<float, true>"),
+                "c1n5": ("k_cpb<true>", "k_cpb<float, true>"), "m7x32": ("k_cpb<false>", "k_cpb<float, false>")}
+ENTRY_SEEDS = {"bin7": 1, "main": 22}  # the stand-alone entry points project the crafted dual itself
+T_OFFSET = 50.0
+ITERS = (0, 2)  # max_iters of the two runs of every case: one iteration, three iterations
+
+
+def _uniform(C):
+    return np.full((C, C), 1.0 / C), np.full(C, 1.0 / C)
+
+
+def _synthetic(C, N, nx, nu, seed):
+    P, v = _uniform(C)
+    return recipe_synthetic(P, v, N, N, nx, nu, seed=seed)
+
+
+def _seven_modes():
+    """31 nodes, binary branching, 7 Markov modes (each with two successors) at 32 / 12 with a cost
+    per mode: 7 sqrtQ and 7 sqrtR tables, 37 KB in float and 75 KB in double, beyond the 32 KiB of
+    LDS the batch kernel stages its tables in, so it reaches k_cpb<false> and k_cpb<float, false>
+    (every mode must occur for its table to be packed, which takes 4 stages from 2 initial modes)."""
+    M = 7
+    P = np.zeros((M, M))
+    for i in range(M):
+        P[i, i] = P[i, (i + 1) % M] = 0.5
+    v = np.zeros(M)
+    v[0] = v[3] = 0.5
+    r = recipe_synthetic(P, v, 4, 4, 32, 12, seed=9)
+    r["Q"] = np.array([(1.0 + k) * q for k, q in enumerate(r["Q"])])
+    r["R"] = np.array([(2.0 + k) * q for k, q in enumerate(r["R"])])
+    return r
+
+
+# name -> recipe; "-nobox" drops every box, "-leafbox" the nonleaf ones
+_TREES = {
+    "bin3": lambda: _synthetic(2, 3, 20, 8, 11),       # 15 nodes
+    "bin4": lambda: _synthetic(2, 4, 20, 8, 22),       # 31 nodes
+    "bin7": lambda: _synthetic(2, 7, 20, 8, 12),       # 255 nodes
+    "bin8": lambda: _synthetic(2, 8, 20, 8, 21),       # 511 nodes
+    "chain12": lambda: _synthetic(1, 12, 20, 8, 3),    # 13 nodes, one leaf
+    "bin32d5": lambda: _synthetic(2, 5, 32, 12, 4),    # 63 nodes
+    "quad20d4": lambda: _synthetic(4, 4, 20, 8, 6),    # 341 nodes
+    "tern32d4": lambda: _synthetic(3, 4, 32, 12, 4),   # 121 nodes
+    "quad64d3": lambda: _synthetic(4, 3, 64, 16, 7),   # 85 nodes
+    "m7x32": _seven_modes,                             # 31 nodes, tables beyond the batch kernel's LDS
+}
+
+
+@functools.lru_cache(maxsize=None)
+def problem(tree):
+    """(recipe, RAOCP problem, OracleProblem, alpha) of a tree, built once. alpha: the golden
+    fixtures' pinned step size, else the oracle's own (0.999 / lambda_max by ARPACK)."""
+    from oracle.raocp_oracle import OracleProblem
+    base, _, variant = tree.partition("-")
+    if base in GOLDEN_FILE:
+        z = np.load(os.path.join(GOLDEN, GOLDEN_FILE[base] + ".npz"))
+        r = recipe_from_npz(z, base)
+        alpha = float(z[f"{base}/cp_alpha"])
+    else:
+        r = _TREES[base]()
+        alpha = None
+    if variant in ("nobox", "leafbox"):
+        r["nl_min"] = r["nl_max"] = None
+        if variant == "nobox":
+            r["l_min"] = r["l_max"] = None
+    else:
+        assert variant == "", tree
+    _, prob = build_problem(r)
+    op = OracleProblem(prob)
+    if alpha is None:
+        alpha = op.step_size()[1]
+    return r, prob, op, alpha
+
+
+def seed_of(tree):
+    return SEEDS.get(tree.partition("-")[0], SEED)
+
+
+def rotations(tree):
+    return crafted_rotations(problem(tree)[2])
+
+
+@functools.lru_cache(maxsize=None)
+def start(tree, rot, seed, f32=False):
+    """(p0, d0, child classes, leaf classes) of the tree's crafted start, read-only. f32: the
+    start rounded to float, which is what a float context holds after set_primal / set_dual."""
+    r, prob, op, alpha = problem(tree)
+    p0, d0, ccls, lcls = crafted_start(op, alpha, seed, T_OFFSET, rot)
+    if f32:
+        p0, d0 = p0.astype(np.float32).astype(np.float64), d0.astype(np.float32).astype(np.float64)
+    for a in (p0, d0, ccls, lcls):
+        a.setflags(write=False)
+    return p0, d0, ccls, lcls
+
+
+@functools.lru_cache(maxsize=None)
+def reference(tree, K, rot, seed, f32=False, x0_scale=1.0):
+    """OracleProblem.chock(x0_scale * x0, K, 0.0, alpha, p0, d0) from the crafted start: (status,
+    err, derr, z, eta), computed once and read-only."""
+    r, prob, op, alpha = problem(tree)
+    p0, d0, _, _ = start(tree, rot, seed, f32)
+    x0 = x0_scale * np.asarray(r["x0"], dtype=float).reshape(-1)
+    st, err, derr, z, e, _ = op.chock(x0, K, 0.0, alpha=alpha, p0=p0, d0=d0)
+    for a in (err, derr, z, e):
+        a.setflags(write=False)
+    return st, err, derr, z, e
+
+
+@functools.lru_cache(maxsize=None)
+def census(tree, rot, seed):
+    """The oracle's branch census of iteration 1 from the crafted start."""
+    r, prob, op, alpha = problem(tree)
+    p0, d0, _, _ = start(tree, rot, seed)
+    v = op.chock_modified_duals(r["x0"], 0, alpha, p0=p0, d0=d0)[0]
+    return op.branch_census(v)
+
+
+# golden main's leaf box is +-7 on a state of order 1: a standard normal start cannot reach its lo
+# or hi branch (its nonleaf box, +-0.1 on the inputs, is left on both sides). The leaf-box sites of
+# the kernels main runs (scalar, batch) are reached on bin7, bin6 and c1n5.
+BOX_EXEMPT = {"main": ("box_l",)}
+
+
+def box_exempt(tree):
+    return BOX_EXEMPT.get(tree.partition("-")[0], ())
+
+
+def census_violations(op, cens, exempt=()):
+    """The conditions a crafted start must meet in iteration 1, checked on the census of each of
+    its rotations (cens); returns the list of those it misses (empty: a valid start).
+      - each SOC class on >= 30 % of the child cones and of the leaf cones (over the rotations);
+      - every margin >= 0.1;
+      - every (child slot within its parent, class) pair;
+      - each box branch on >= 5 % of the boxed entries, for the nonleaf boxes (eta7) and the leaf
+        boxes (eta14) separately, since they are separate code in every kernel (exempt: the kinds
+        of BOX_EXEMPT, which the caller names);
+      - each sign on >= 10 % of the clamped eta1 and eta2 entries."""
+    bad = []
+    for kind in ("child", "leaf"):
+        cls = np.concatenate([c[kind + "_class"] for c in cens])
+        share = np.bincount(cls, minlength=3) / cls.size
+        if share.min() < 0.30:
+            bad.append(f"{kind} cone classes {np.round(share, 3).tolist()} < 30 %")
+        mar = min(float(c[kind + "_margin"].min()) for c in cens)
+        if mar < 0.1:
+            bad.append(f"{kind} cone margin {mar:.3g} < 0.1")
+    rank = op.rank[op.kids]
+    pairs = {(int(s), int(k)) for c in cens for s, k in zip(rank, c["child_class"])}
+    missing = {(s, k) for s in range(int(op.nch.max())) for k in range(3)} - pairs
+    if missing:
+        bad.append(f"(child slot, class) pairs missing: {sorted(missing)}")
+    for q, c in enumerate(cens):
+        for key in ("box_nl", "box_l"):
+            box = c[key]
+            if key not in exempt and box.sum() and box.min() < 0.05 * box.sum():
+                bad.append(f"start {q}: {key} lo / hi / inside {box.tolist()} < 5 %")
+        for key, total in (("eta1_sign", op.y_all.size - op.m), ("eta2_sign", op.m)):
+            if c[key].min() < 0.10 * total:
+                bad.append(f"start {q}: {key} + / - {c[key].tolist()} of {total} < 10 %")
+    return bad
+
+
+TIE_TREES = ("bin7", "main", "chain12")
+
+
+@functools.lru_cache(maxsize=None)
+def tie_dual(tree, seed=9):
+    """A dual on the edges of the projections' comparisons. Five kinds of cone in turn over the
+    child cones and over the leaf cones: F = 0 with t = 2, t = 0, t = -2; nf == t and nf == -t
+    held exactly (F = (3, 0, .., 0, 4) with the 4 in the cone's last F entry, eta5 / eta12, so
+    that the norm spans its segments; 9 + 16 = 25 is exact in any summation order and in either
+    precision; t = 5, -5). Of every box row, one entry in three sits exactly at lo and the next
+    exactly at hi. Returns (v, child cone entry indices [cones, F.. t], which child cones the
+    projection must return unchanged (the others it must zero), and the same two for the leaf cones)."""
+    r, prob, op, alpha = problem(tree)
+    nx, nu = op.nx, op.nu
+    rng = np.random.default_rng(seed)
+    v = np.where(op.live_masks()[1], rng.standard_normal(op.D), 0.0)
+    j, lf = op.kids, op.leaves
+    child = np.concatenate([op.E3[j][:, None] + np.arange(nx), op.E4[j][:, None] + np.arange(nu),
+                            op.E5[j][:, None], op.E6[j][:, None]], axis=1)
+    leaf = np.concatenate([op.E11[lf][:, None] + np.arange(nx), op.E12[lf][:, None], op.E13[lf][:, None]], axis=1)
+    keeps = []
+    for idx in (child, leaf):
+        kind = np.arange(idx.shape[0]) % 5
+        v[idx[:, :-1]] = 0.0
+        v[idx[kind >= 3, 0]] = 3.0
+        v[idx[kind >= 3, -2]] = 4.0
+        v[idx[:, -1]] = np.array([2.0, 0.0, -2.0, 5.0, -5.0])[kind]
+        keeps.append(np.isin(kind, (0, 1, 3)))
+    act, lact = np.flatnonzero(op.nl_active), np.flatnonzero(op.l_active)
+    for idx, lo, hi in ((op.E7[act][:, None] + np.arange(nx + nu), op.nl_lo[act], op.nl_hi[act]),
+                        (op.E14[lf[lact]][:, None] + np.arange(nx), op.l_lo[lact], op.l_hi[lact])):
+        if idx.size:
+            col = np.arange(idx.shape[1])[None, :] + np.arange(idx.shape[0])[:, None]
+            v[idx] = np.where(col % 3 == 0, lo, np.where(col % 3 == 1, hi, v[idx]))
+    v.setflags(write=False)
+    return v, child, keeps[0], leaf, keeps[1]
+
+
+# ---- the kernel families (tests/test_gpu_branches.py). A case: id, tree, the environment its
+# context is created under (as the family's own test file selects it), dtype, and what
+# kernel_info must report: (op, "eq" | "starts", text).
+_DRC = [(11, "eq", "k_drc<20, 8, 2>")]
+_CP6 = [(11, "eq", ""), (9, "eq", "k_dr<20, 8> x1"), (10, "eq", "k_cp6<double, 20, 8, 2>")]
+_CP4 = [(11, "eq", ""), (10, "eq", "k_cp4<double, 20, 8>")]
+_CP3_20 = [(11, "eq", ""), (10, "starts", "k_cp3<double, 20, 8")]
+_NO6, _NO4 = {"RAOCP_DRC": "0", "RAOCP_CP6": "0"}, {"RAOCP_DRC": "0", "RAOCP_CP6": "0", "RAOCP_CP4": "0"}
+_MFMA = {"RAOCP_CP3": "0", "RAOCP_CP_V1": "0"}
+_SCALAR = {"RAOCP_CP3": "0", "RAOCP_CP_V1": "1"}
+
+FAMILIES = [
+    ("drc-bin4", "bin4", {"RAOCP_DR_CUTS": ""}, "float64", _DRC),
+    ("drc-bin4-nobox", "bin4-nobox", {"RAOCP_DR_CUTS": ""}, "float64", _DRC),
+    ("drc-bin8", "bin8", {"RAOCP_DR_CUTS": "4"}, "float64", _DRC),
+    ("drc-bin8-nobox", "bin8-nobox", {"RAOCP_DR_CUTS": "4"}, "float64", _DRC),
+    ("cp6-bin3", "bin3", {"RAOCP_DRC": "0"}, "float64", _CP6),
+    ("cp6-bin3-nobox", "bin3-nobox", {"RAOCP_DRC": "0"}, "float64", _CP6),
+    ("cp6-bin7", "bin7", {"RAOCP_DRC": "0"}, "float64", _CP6),
+    ("cp6-bin7-nobox", "bin7-nobox", {"RAOCP_DRC": "0"}, "float64", _CP6),
+    ("cp6-bin4", "bin4", {"RAOCP_DRC": "0", "RAOCP_DR_CUTS": ""}, "float64", _CP6),
+    ("cp6-bin8", "bin8", {"RAOCP_DRC": "0", "RAOCP_DR_CUTS": "4"}, "float64", _CP6),
+    ("cp4-bin7", "bin7", _NO6, "float64", _CP4),
+    ("cp4-bin7-leafbox", "bin7-leafbox", _NO6, "float64", _CP4),
+    ("cp4-bin8", "bin8", dict(_NO6, RAOCP_DR_CUTS="4"), "float64", _CP4),
+    ("cp3-bin7-split1", "bin7", dict(_NO4, RAOCP_CP3_SPLIT="1"), "float64", _CP3_20),
+    ("cp3-bin7-split0", "bin7", dict(_NO4, RAOCP_CP3_SPLIT="0"), "float64", _CP3_20),
+    ("cp3-bin8", "bin8", dict(_NO4, RAOCP_DR_CUTS="4"), "float64", _CP3_20),
+    ("cp3-chain12", "chain12", {}, "float64", _CP3_20),
+    ("cp3-bin32d5", "bin32d5", {}, "float64", [(10, "starts", "k_cp3<double, 32, 12")]),
+    ("mfma-bin7", "bin7", _MFMA, "float64", [(10, "eq", "k_cpd2<double, 2, 1> + k_cpp2<double, 2, 1>")]),
+    ("scalar-bin7", "bin7", _SCALAR, "float64", [(10, "eq", "k_cpd<double, 20, 8> + k_cpp<double, 20, 8>")]),
+    ("scalar-main", "main", _SCALAR, "float64", [(10, "eq", "k_cpd<double, 3, 2> + k_cpp<double, 3, 2>")]),
+    ("cp5-quad20d4", "quad20d4", {}, "float64", [(10, "starts", "k_cp5_leaf<double, 20, 4> x1 + k_cp5_fams<double, 20, 8, 4>")]),
+    ("cp5-tern32d4", "tern32d4", {}, "float64", [(10, "starts", "k_cp5_leaf<double, 32, 3> x1 + k_cp5_fams<double, 32, 12, 3>")]),
+    ("cp3-quad20d4", "quad20d4", {"RAOCP_CP5": "0"}, "float64", _CP3_20[1:]),
+    ("cp3-tern32d4", "tern32d4", {"RAOCP_CP5": "0"}, "float64", [(10, "starts", "k_cp3<double, 32, 12")]),
+    ("f32-cp5-quad64d3", "quad64d3", {}, "float32", [(10, "starts", "k_cp5_leaf<float, 64, 4> x1 + k_cp5_fams<float, 64, 16, 4>")]),
+    ("f32-cp3-quad64d3", "quad64d3", {"RAOCP_CP5": "0"}, "float32", [(10, "starts", "k_cp3<float, 64, 16")]),
+    ("f32-cp3-bin7", "bin7", {}, "float32", [(10, "starts", "k_cp3<float, 20, 8")]),
+]
+FAMILY = {c[0]: c for c in FAMILIES}
+
+# kernels that claim to share arithmetic, and the bound the suite already holds them to
+AGREE = [
+    ("drc-bin8", "cp6-bin8", 1e-12), ("cp6-bin8", "cp4-bin8", 1e-12), ("cp6-bin8", "cp3-bin8", 1e-12),
+    ("drc-bin4", "cp6-bin4", 1e-12),
+    ("cp6-bin7", "cp4-bin7", 1e-12), ("cp6-bin7", "cp3-bin7-split1", 1e-12), ("cp3-bin7-split1", "cp3-bin7-split0", 1e-12),
+    ("cp5-quad20d4", "cp3-quad20d4", 1e-12), ("cp5-tern32d4", "cp3-tern32d4", 1e-12),
+    ("mfma-bin7", "cp3-bin7-split1", 1e-10),
+]
+
+BATCH_TREES = tuple(BATCH_SEEDS)
+ENTRY_TREES = tuple(ENTRY_SEEDS)
+
+# every (tree, seed) some CP loop on the GPU starts from: the census test covers them all
+CENSUS_CASES = sorted({(c[1], seed_of(c[1])) for c in FAMILIES} | {(t, s) for t in BATCH_TREES for s in BATCH_SEEDS[t]})
