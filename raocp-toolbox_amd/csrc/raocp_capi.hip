@@ -428,7 +428,7 @@ struct DynOp {
             return ta;
         };
         auto tier_blocks = [&](int k) { return sharded ? c->tier_own[k].second : c->tiers[k].nsub; };
-        if (s > 0 && c->dyn_split && !sharded && part == 0) {
+        if (c->path.dyn == DynPath::TiersSplit) {
             // the tiered sweep in two launches (raocp_dynf.hip): one workgroup per subtree of
             // every tier plus the top; k_dyn_up runs the deferred stopping test in block 0
             raocp::FuseArg fa = c->fuse;
@@ -444,7 +444,7 @@ struct DynOp {
             kd<<<nsub + 1, raocp::kFuseBlock, c->lds_down, c->stream>>>(dev_for(), bf, ctl, zsel, c->d, c->x0, fa);
             return;
         }
-        if (s > 0) {
+        if (c->path.dyn == DynPath::Tiers) {
             // tiers below the top, deepest first (backward), the top, then the tiers (forward)
             if (part != 2)
                 for (int k = (int)c->tiers.size() - 1; k >= 0; --k) {
@@ -514,57 +514,47 @@ struct DynOp {
 // launch (only where defer_check(c) holds)
 void launch_dynamics(raocp_ctx* c, raocp::Bufs bf, int zsel, const Ctl* ctl, int part = 0,
                      const raocp::ChkArg* ck = nullptr) {
-    if (c->dr && c->sh_S == 0 && part == 0) {  // the regular-tree sweep (raocp_dynr.hip)
-        raocp::DrPlan p = c->drp;
-        if (c->dev.stamps) p.stamps = c->dev.stamps;
-        raocp::dr_launch(p, c->nx, c->nu, c->dr_lds, bf, zsel, ctl,
-                         ck ? *ck : raocp::ChkArg{nullptr, nullptr, nullptr, 0, 0}, c->stream);
-        return;
+    double* z = zsel % 3 == 0 ? bf.z0 : (zsel % 3 == 1 ? bf.z1 : bf.z2);
+    switch (c->path.dyn) {
+        case DynPath::Dr: {  // the regular-tree sweep (raocp_dynr.hip): never a shard's, so always whole
+            raocp::DrPlan p = c->drp;
+            if (c->dev.stamps) p.stamps = c->dev.stamps;
+            raocp::dr_launch(p, c->nx, c->nu, c->dr_lds, bf, zsel, ctl,
+                             ck ? *ck : raocp::ChkArg{nullptr, nullptr, nullptr, 0, 0}, c->stream);
+            return;
+        }
+        case DynPath::Dyn3: launch_dyn3(c, z, ctl, ck, part); return;
+        case DynPath::Dyn2:
+            if (c->f32) dispatch_rt(c->nx, c->nu, Dyn2Op<float>{}, c, z, ctl);
+            else dispatch_rt(c->nx, c->nu, Dyn2Op<double>{}, c, z, ctl);
+            return;
+        default: dispatch(c->nx, c->nu, DynOp{}, c, bf, zsel, ctl, part, ck); return;  // TiersSplit, Tiers, PerStage
     }
-    if (c->dyn3) {
-        double* z = zsel % 3 == 0 ? bf.z0 : (zsel % 3 == 1 ? bf.z1 : bf.z2);
-        launch_dyn3(c, z, ctl, ck, part);
-        return;
-    }
-    if (c->dyn2) {
-        double* z = zsel % 3 == 0 ? bf.z0 : (zsel % 3 == 1 ? bf.z1 : bf.z2);
-        if (c->f32) dispatch_rt(c->nx, c->nu, Dyn2Op<float>{}, c, z, ctl);
-        else dispatch_rt(c->nx, c->nu, Dyn2Op<double>{}, c, z, ctl);
-        return;
-    }
-    dispatch(c->nx, c->nu, DynOp{}, c, bf, zsel, ctl, part, ck);
 }
 
 // the device word a hand-off sweep sets when a wait times out (nullptr: no such sweep)
 const unsigned* err_word(const raocp_ctx* c) {
-    if (c->dr && c->sh_S == 0) return c->drp.sync + 1;
-    if (c->dyn_split && c->fuse_sync) return (const unsigned*)c->fuse_sync + 1;
+    if (c->path.dyn == DynPath::Dr) return c->drp.sync + 1;
+    if (c->path.dyn == DynPath::TiersSplit && c->fuse_sync) return (const unsigned*)c->fuse_sync + 1;
     return nullptr;
 }
 // the fused sweep's error word (a hand-off wait timed out, raocp_dynf.hip): checked after
 // every synchronised run that may have launched it; the context is unusable afterwards
 int fuse_err(raocp_ctx* c) {
-    if (c->dr && c->sh_S == 0) {
-        unsigned e = 0;
-        HIPCHK(hipMemcpy(&e, c->drp.sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (e) {
-            // clear the epoch, the error word and every granule: the next projection starts
-            // from a clean protocol state
-            HIPCHK(hipMemset(c->drp.sync, 0, 2 * sizeof(unsigned)));
-            HIPCHK(hipMemset(c->drp.gq, 0, c->dr_gran * sizeof(unsigned long long)));
-            HIPCHK(hipMemset(c->drp.gx, 0, c->dr_gran * sizeof(unsigned long long)));
-            return fail(RAOCP_ERR_STATE, "dynamics sweep: a workgroup hand-off timed out (k_dr); "
-                                         "RAOCP_DR=0 selects the tiered sweep");
-        }
-        return RAOCP_OK;
+    const unsigned* w = err_word(c);
+    unsigned e = 0;
+    if (w) HIPCHK(hipMemcpy(&e, w, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (!e) return RAOCP_OK;
+    if (c->path.dyn == DynPath::Dr) {  // a clean protocol state: the epoch, the error word and every granule
+        HIPCHK(hipMemset(c->drp.sync, 0, 2 * sizeof(unsigned)));
+        HIPCHK(hipMemset(c->drp.gq, 0, c->dr_gran * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(c->drp.gx, 0, c->dr_gran * sizeof(unsigned long long)));
+        return fail(RAOCP_ERR_STATE, "dynamics sweep: a workgroup hand-off timed out (k_dr); "
+                                     "RAOCP_DR=0 selects the tiered sweep");
     }
-    if (!c->dyn_split || !c->fuse_sync) return RAOCP_OK;
-    int e = 0;
-    HIPCHK(hipMemcpy(&e, c->fuse_sync + 1, sizeof(int), hipMemcpyDeviceToHost));
-    if (e) HIPCHK(hipMemset(c->fuse_sync, 0, c->fuse_words * sizeof(unsigned)));  // clean protocol state
-    if (e) return fail(RAOCP_ERR_STATE, "dynamics sweep: a workgroup hand-off timed out (k_dyn_up / k_dyn_down); "
-                                        "RAOCP_DYN_SPLIT=0 selects the tier launches");
-    return RAOCP_OK;
+    HIPCHK(hipMemset(c->fuse_sync, 0, c->fuse_words * sizeof(unsigned)));
+    return fail(RAOCP_ERR_STATE, "dynamics sweep: a workgroup hand-off timed out (k_dyn_up / k_dyn_down); "
+                                 "RAOCP_DYN_SPLIT=0 selects the tier launches");
 }
 
 // role: 0 all blocks; 1 nonleaf blocks only; 2 leaf blocks only (op_bench timing)
@@ -740,34 +730,44 @@ int cp3_image(raocp_ctx* c) {
     if (c->nx == 20) return cp3_imaget<double, 20, 8>(c);
     return cp3_imaget<double, 32, 12>(c);
 }
-void launch_cp3(raocp_ctx* c, int part = 0) {
-    if (c->cp6 && c->sh_S == 0) {
-        raocp::cp6_launch(c->dev, c->ctl, c->bufs, c->redpart, c->box_mode, c->cp5_tk, c->cp6_grid, c->cp3img, c->stream);
-        return;
+// the CP iteration after the dynamics in its fused form (cp_fused(c->path.cp)); sh: a shard's ranges and task lists
+void launch_cp_fused(raocp_ctx* c, int part = 0) {
+    const bool sh = c->sh_S > 0;
+    switch (c->path.cp) {
+        case CpPath::Cp6:
+            raocp::cp6_launch(c->dev, c->ctl, c->bufs, c->redpart, c->box_mode, c->cp5_tk, c->cp6_grid, c->cp3img, c->stream);
+            return;
+        case CpPath::Cp5:
+            // a shard: its eta2 tasks, leaves and families, then (part 1, after X1) the cut's parents
+            if (part == 0)
+                raocp::cp5_launch(c->dev, c->ctl, c->bufs, c->redpart, c->unif_C, c->box_mode, c->cp5_et,
+                                  sh ? c->own_lo[c->N] : c->m, sh ? c->own_hi[c->N] : c->n, c->cp5_gl, c->cp5_tk, c->cp5_gf,
+                                  c->cp3img, c->cp5_lpf, c->stream);
+            else
+                raocp::cp5_launch(c->dev, c->ctl, c->bufs, c->redpart + (size_t)raocp::cp5_rows(c->cp5_gl, c->cp5_gf) * 6,
+                                  c->unif_C, c->box_mode, c->cp5_et, 0, 0, 0, c->cp5_tkb, c->cp5_gfb, c->cp3img, c->cp5_lpf,
+                                  c->stream);
+            return;
+        case CpPath::Cp4:
+            raocp::cp4_launch(c->dev, c->ctl, c->bufs, c->redpart, c->unif_C, c->box_mode, c->cp3_ta, c->cp3img, c->cp3_grid,
+                              c->cp4_wpb, c->stream);
+            return;
+        case CpPath::Cp3:
+            if (sh)
+                launch_cp3t<true>(c, part ? c->cp3_gridb : c->cp3_grid, c->redpart + (part ? (size_t)c->cp3_grid * 6 : 0),
+                                  part ? c->cp3_tb : c->cp3_ta);
+            else
+                launch_cp3t<false>(c, c->cp3_grid, c->redpart, c->cp3_ta);
+            return;
+        default: return;  // not a fused form: launch_cp_after_sweep
     }
-    if (c->cp5) {
-        // a shard: its eta2 tasks, leaves and families, then (part 1, after X1) the cut's parents
-        const bool sh = c->sh_S > 0;
-        if (part == 0)
-            raocp::cp5_launch(c->dev, c->ctl, c->bufs, c->redpart, c->unif_C, c->box_mode, c->cp5_et,
-                              sh ? c->own_lo[c->N] : c->m, sh ? c->own_hi[c->N] : c->n, c->cp5_gl, c->cp5_tk, c->cp5_gf,
-                              c->cp3img, c->cp5_lpf, c->stream);
-        else
-            raocp::cp5_launch(c->dev, c->ctl, c->bufs, c->redpart + (size_t)raocp::cp5_rows(c->cp5_gl, c->cp5_gf) * 6,
-                              c->unif_C, c->box_mode, c->cp5_et, 0, 0, 0, c->cp5_tkb, c->cp5_gfb, c->cp3img, c->cp5_lpf,
-                              c->stream);
-        return;
-    }
-    if (c->cp4 && c->sh_S == 0) {
-        raocp::cp4_launch(c->dev, c->ctl, c->bufs, c->redpart, c->unif_C, c->box_mode, c->cp3_ta, c->cp3img, c->cp3_grid,
-                          c->cp4_wpb, c->stream);
-        return;
-    }
-    if (c->sh_S > 0)
-        launch_cp3t<true>(c, part ? c->cp3_gridb : c->cp3_grid, c->redpart + (part ? (size_t)c->cp3_grid * 6 : 0),
-                          part ? c->cp3_tb : c->cp3_ta);
-    else
-        launch_cp3t<false>(c, c->cp3_grid, c->redpart, c->cp3_ta);
+}
+// the CP kernels after the sweep: the fused form, or k_cpd* then k_cpp*. half 0: all of it; a
+// shard launches half 1 before its X1 exchange and half 2 after it
+void launch_cp_after_sweep(raocp_ctx* c, int half = 0) {
+    if (raocp::cp_fused(c->path.cp)) return launch_cp_fused(c, half == 2 ? 1 : 0);
+    if (half != 2) launch_cpd(c);
+    if (half != 1) launch_cpp(c);
 }
 // the solve's first half step Z[1] = prox-part(Z[0] - alpha L^T E[0]) (s_0 relaxation,
 // kernel projection): k_cp_primal; an fp32 context runs k_cpp2 on {p = z+ = Z[0], d = eta+ =
@@ -790,11 +790,14 @@ void launch_first_half(raocp_ctx* c) {
 // z+_k = Z[k % 3] or eta+_k = E[k % 2]), and every later kernel exits on ctl->done, so the
 // result and the history are those of the eager test.
 bool defer_check(const raocp_ctx* c) {
-    if (c->dr && c->sh_S == 0) return !(c->comm || c->sh_R != 1 || c->no_defer_check);
-    if (c->dyn3 && c->sh_S == 0) return !(c->comm || c->sh_R != 1 || c->no_defer_check || c->N < 1);
-    if (c->comm || c->sh_R != 1 || c->dyn2 || c->cut <= 0 || c->tiers.empty() || c->no_defer_check)
-        return false;
-    return c->tiers.back().nsub > 0;
+    if (c->comm || c->sh_R != 1 || c->no_defer_check) return false;
+    switch (c->path.dyn) {  // the sweeps whose first launch can carry the test
+        case DynPath::Dr: return true;
+        case DynPath::Dyn3: return c->N >= 1;
+        case DynPath::TiersSplit:
+        case DynPath::Tiers: return !c->tiers.empty() && c->tiers.back().nsub > 0;
+        default: return false;
+    }
 }
 
 // ---- RCCL, loaded on demand (dlopen) so single-GPU users never load it
@@ -835,9 +838,10 @@ int rccl_load() {
 // share a process (raocp_group_cp_run), host-driven copies between the phases.
 // X2 rows: the tiered sweep's q rows (KP doubles each), or the per-stage sweep's (nx scalars
 // of the context's type, raocp_dyn3.hip)
-int x2_row(const raocp_ctx* c) { return c->dyn3 ? c->nx : c->KP; }
-int x2_elt(const raocp_ctx* c) { return c->dyn3 ? c->wsz : 8; }
-double* x2_q(const raocp_ctx* c) { return c->dyn3 ? c->Q2 : c->q; }
+bool x2_dyn3(const raocp_ctx* c) { return c->path.dyn == DynPath::Dyn3; }
+int x2_row(const raocp_ctx* c) { return x2_dyn3(c) ? c->nx : c->KP; }
+int x2_elt(const raocp_ctx* c) { return x2_dyn3(c) ? c->wsz : 8; }
+double* x2_q(const raocp_ctx* c) { return x2_dyn3(c) ? c->Q2 : c->q; }
 size_t x2_bytes(const raocp_ctx* c) { return (size_t)c->x_max * x2_row(c) * x2_elt(c); }
 void shard_pack_x2(raocp_ctx* c) {
     const size_t row = (size_t)x2_row(c) * x2_elt(c);
@@ -865,7 +869,7 @@ struct X1Src {
     int oa, ob;
 };
 X1Src x1_src(const raocp_ctx* c) {
-    if (c->cp5) return X1Src{c->bufs.z2, c->bufs.e1, c->dev.S0, c->dev.E2};
+    if (c->path.cp == CpPath::Cp5) return X1Src{c->bufs.z2, c->bufs.e1, c->dev.S0, c->dev.E2};
     return X1Src{c->bufs.e1, c->XI2, c->dev.E2, c->dev.E2};
 }
 void shard_pack_x1(raocp_ctx* c) {
@@ -895,28 +899,38 @@ int rccl_check(ncclResult_t r, const char* what) {
     return RAOCP_OK;
 }
 
+// the three phases of a shard's CP iteration; the transport (RCCL in enqueue_shard_iteration, device copies in
+// raocp_group_cp_run) moves x2_send -> x2_recv after the first and x1_send -> x1_recv after the second
+void shard_phase_back(raocp_ctx* c) {  // the backward sweep below the cut, its roots' q rows packed
+    launch_dynamics(c, c->bufs, 1, c->ctl, 1);
+    shard_pack_x2(c);
+}
+void shard_phase_fwd(raocp_ctx* c) {  // the top and the forward sweep, the first CP launch, X1 packed
+    shard_unpack_x2(c);
+    launch_dynamics(c, c->bufs, 1, c->ctl, 2);
+    launch_cp_after_sweep(c, 1);
+    shard_pack_x1(c);
+}
+void shard_phase_top(raocp_ctx* c) {  // the second CP launch (the previous iteration's stopping test first)
+    shard_unpack_x1(c);
+    launch_cp_after_sweep(c, 2);
+    raocp::k_cp_reduce<<<1, kBlock, 0, c->stream>>>(c->ctl, c->redpart, c->cp_rows, c->red8);
+}
+
 // one CP iteration of a shard whose transport is RCCL (graph-capturable)
 int enqueue_shard_iteration(raocp_ctx* c) {
     ncclComm_t comm = (ncclComm_t)c->comm;
     int rc;
-    launch_dynamics(c, c->bufs, 1, c->ctl, 1);
-    shard_pack_x2(c);
+    shard_phase_back(c);
     if ((rc = rccl_check(g_rccl.all_gather(c->x2_send, c->x2_recv, (size_t)c->x_max * x2_row(c),
                                            x2_elt(c) == 4 ? ncclFloat32 : ncclFloat64, comm, c->stream),
                          "ncclAllGather(q)")))
         return rc;
-    shard_unpack_x2(c);
-    launch_dynamics(c, c->bufs, 1, c->ctl, 2);
-    if (c->cp3) launch_cp3(c, 0);
-    else launch_cpd(c);
-    shard_pack_x1(c);
+    shard_phase_fwd(c);
     if ((rc = rccl_check(g_rccl.all_gather(c->x1_send, c->x1_recv, (size_t)x1_len(c), ncclFloat64, comm, c->stream),
                          "ncclAllGather(eta2, residuals)")))
         return rc;
-    shard_unpack_x1(c);  // + the previous iteration's stopping test
-    if (c->cp3) launch_cp3(c, 1);
-    else launch_cpp(c);
-    raocp::k_cp_reduce<<<1, kBlock, 0, c->stream>>>(c->ctl, c->redpart, c->cp_rows, c->red8);
+    shard_phase_top(c);
     return RAOCP_OK;
 }
 
@@ -933,7 +947,6 @@ int enqueue_shard_tail(raocp_ctx* c) {
     return RAOCP_OK;
 }
 
-// returns the first failure of an RCCL call (launch errors surface at the next sync)
 // k_drc's residual rows of iteration parity q, and the ctl->flags bit of its NaN-in-box flag
 double* drc_part(raocp_ctx* c, int q) { return c->redpart + (size_t)(q & 1) * c->cp_rows * 6; }
 int drc_nanbit(int q) { return 2 << (q & 1); }
@@ -944,6 +957,12 @@ void launch_drc(raocp_ctx* c, int it, bool with_check) {
     const raocp::ChkArg ck{c->ctl, c->hist, drc_part(c, it - 1), c->cp_rows, with_check ? 1 : 0, drc_nanbit(it - 1)};
     raocp::drc_launch(p, c->d_drca + (it & 1), c->drca.box, c->drc_lds, c->bufs, ck, c->stream);
 }
+// iteration `it`'s stopping test as a launch of its own (k_drc's residual rows and NaN bit go by parity)
+void launch_cp_check(raocp_ctx* c, int it, raocp::CtlPub* pub, const unsigned* ew) {
+    const bool f = c->path.fused;
+    raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, f ? drc_part(c, it) : c->redpart, c->cp_rows,
+                                                   f ? drc_nanbit(it) : 0, pub, ew);
+}
 int enqueue_cp_iteration(raocp_ctx* c, int it) {
     const raocp::Bufs keep = c->bufs;
     c->bufs = rotated(c, it);
@@ -953,23 +972,15 @@ int enqueue_cp_iteration(raocp_ctx* c, int it) {
         return rc;
     }
     const bool defer = defer_check(c);
-    if (c->drc && c->sh_S == 0) {
+    if (c->path.fused) {
         launch_drc(c, it, defer && it > 0);
-        c->bufs = keep;
-        if (!defer)
-            raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, drc_part(c, it), c->cp_rows, drc_nanbit(it), nullptr, nullptr);
-        return RAOCP_OK;
-    }
-    const raocp::ChkArg ck{c->ctl, c->hist, c->redpart, c->cp_rows, 1};
-    launch_dynamics(c, c->bufs, 1, c->ctl, 0, defer && it > 0 ? &ck : nullptr);
-    if (c->cp3) {
-        launch_cp3(c);
     } else {
-        launch_cpd(c);
-        launch_cpp(c);
+        const raocp::ChkArg ck{c->ctl, c->hist, c->redpart, c->cp_rows, 1};
+        launch_dynamics(c, c->bufs, 1, c->ctl, 0, defer && it > 0 ? &ck : nullptr);
+        launch_cp_after_sweep(c);
     }
     c->bufs = keep;
-    if (!defer) raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, c->redpart, c->cp_rows, 0, nullptr, nullptr);
+    if (!defer) launch_cp_check(c, it, nullptr, nullptr);
     return RAOCP_OK;
 }
 // k_cpb (raocp_cpb.hip) covers this context's batched solves: unsharded, sizes within the
@@ -1042,79 +1053,80 @@ std::string kernel_name(const raocp_ctx* c, int op) {
                 terms.push_back({k, 1});
             };
             auto b = [](bool v) { return std::string(v ? "true" : "false"); };
-            if (c->dr && c->sh_S == 0) {
-                return std::string(raocp::dr_name(c->nx, c->nu)) + " x1";
-            } else if (c->dyn3) {  // a backward and a forward launch per nonleaf stage below the top
-                const int ts = dyn3_top_stages(c);
-                for (int t = ts; t < c->N; ++t) add("k_dy3_back<" + T + ", " + nn + ">");
-                if (ts) add("k_dy3_top_back<" + T + ", " + nn + ">");
-                if (ts) add("k_dy3_top_fwd<" + T + ", " + nn + ">");
-                for (int t = ts; t < c->N; ++t) add("k_dy3_fwd<" + T + ", " + nn + ">");
-            } else if (c->dyn2) {
-                return "k_d2_prod + k_d2_node + k_d2_x0 + k_d2_fwd (per stage, " + T + ")";
-            } else if (c->cut > 0 && c->dyn_split && c->sh_S == 0) {
-                return "k_dyn_up<" + nn + "> x1 + k_dyn_down<" + nn + ", " + b(c->f_lds_top) + "> x1";
-            } else if (c->cut > 0) {
-                for (int k = (int)c->tiers.size() - 1; k >= 0; --k)
-                    add("k_dyn_bottom_back<" + nn + ", " + b(c->tiers[k].fold) + ">");
-                add("k_dyn_top<" + nn + ", " + b(c->f_lds_top) + ", " + b(c->fold_top) + ">");
-                for (const auto& tp : c->tiers) add("k_dyn_bottom_fwd<" + nn + ", " + std::to_string(tp.fm) + ">");
-            } else {
-                return "k_dyn_gather + k_dyn_stage_a / _b / _f (per stage)";
+            switch (c->path.dyn) {
+                case DynPath::Dr: return std::string(raocp::dr_name(c->nx, c->nu)) + " x1";
+                case DynPath::Dyn3: {  // a backward and a forward launch per nonleaf stage below the top
+                    const int ts = dyn3_top_stages(c);
+                    for (int t = ts; t < c->N; ++t) add("k_dy3_back<" + T + ", " + nn + ">");
+                    if (ts) add("k_dy3_top_back<" + T + ", " + nn + ">");
+                    if (ts) add("k_dy3_top_fwd<" + T + ", " + nn + ">");
+                    for (int t = ts; t < c->N; ++t) add("k_dy3_fwd<" + T + ", " + nn + ">");
+                    break;
+                }
+                case DynPath::Dyn2: return "k_d2_prod + k_d2_node + k_d2_x0 + k_d2_fwd (per stage, " + T + ")";
+                case DynPath::TiersSplit:
+                    return "k_dyn_up<" + nn + "> x1 + k_dyn_down<" + nn + ", " + b(c->f_lds_top) + "> x1";
+                case DynPath::Tiers:
+                    for (int k = (int)c->tiers.size() - 1; k >= 0; --k)
+                        add("k_dyn_bottom_back<" + nn + ", " + b(c->tiers[k].fold) + ">");
+                    add("k_dyn_top<" + nn + ", " + b(c->f_lds_top) + ", " + b(c->fold_top) + ">");
+                    for (const auto& tp : c->tiers) add("k_dyn_bottom_fwd<" + nn + ", " + std::to_string(tp.fm) + ">");
+                    break;
+                case DynPath::PerStage: return "k_dyn_gather + k_dyn_stage_a / _b / _f (per stage)";
             }
             std::string s;
             for (const auto& t : terms) s += (s.empty() ? "" : " + ") + t.first + " x" + std::to_string(t.second);
             return s;
         }
         case 11:  // the CP loop's fused launch (dynamics projection + CP iteration), if any
-            return c->drc && c->sh_S == 0 ? raocp::drc_name() : "";
-        case 15: {  // the composed maps of the regular-tree sweep that are active ("" when none)
+            return c->path.fused ? raocp::drc_name() : "";
+        case 15:    // the composed maps of the regular-tree sweep that are active ("" when none)
+        case 16: {  // ... its composed forward maps
             std::string s;
-            if (c->dr && c->sh_S == 0)
-                for (int k = 0; k < c->drp.T; ++k)
-                    if (c->drp.t[k].xf & raocp::kDrXfMidBack) s += (s.empty() ? "" : " ") + std::string("mid_back_root@") + std::to_string(k);
-            return s;
-        }
-        case 16: {  // the composed forward maps of the regular-tree sweep that are active ("" when none)
-            std::string s;
-            if (c->dr && c->sh_S == 0)
-                for (int k = 0; k < c->drp.T; ++k)
-                    if (c->drp.t[k].xf & raocp::kDrXfFwd)
-                        s += (s.empty() ? "" : " ") + std::string(k == c->drp.T - 1 ? "deep_fwd@" : "mid_fwd@") + std::to_string(k);
+            for (int k = 0; k < c->drp.T && c->path.dyn == DynPath::Dr; ++k) {
+                const char* m = op == 15 ? "mid_back_root@" : (k == c->drp.T - 1 ? "deep_fwd@" : "mid_fwd@");
+                if (c->drp.t[k].xf & (op == 15 ? raocp::kDrXfMidBack : raocp::kDrXfFwd)) s += (s.empty() ? "" : " ") + std::string(m) + std::to_string(k);
+            }
             return s;
         }
         case 12:  // the forms of the k_cp5 launches, when they run ("" otherwise)
-            if (!c->cp5) return "";
+            if (c->path.cp != CpPath::Cp5) return "";
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
         case 13:  // the batched CP kernel, when raocp_cp_batch_run launches it ("" otherwise)
             return cpb_on(c) ? raocp::cpb_name(c->f32, raocp::cpb_tab_bytes(c->dev, c->f32) > 0) : "";
         case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
             return cpb_on(c) ? raocp::mpc_step_name(c->f32) : "";
-        case 10:
-            if (c->cp6 && c->sh_S == 0) return raocp::cp6_name();
-            if (c->cp5) return std::string(raocp::cp5_name(c->f32, c->nx)) + (c->sh_S > 0 ? " (+ fams x1 after X1)" : "");
-            if (c->cp4 && c->sh_S == 0) return raocp::cp4_name(c->f32, c->nx, c->nu);
-            if (c->cp3) return "k_cp3<" + T + ", " + nn + (c->sh_S > 0 ? ", true> x2" : ", false>");
-            return kernel_name(c, 2) + " + " + kernel_name(c, 6);
+        case 10: {  // a shard launches the fused forms k_cp5 and k_cp3 twice (launch_cp_fused)
+            const bool sh = c->sh_S > 0;
+            switch (c->path.cp) {
+                case CpPath::Cp6: return raocp::cp6_name();
+                case CpPath::Cp5: return std::string(raocp::cp5_name(c->f32, c->nx)) + (sh ? " (+ fams x1 after X1)" : "");
+                case CpPath::Cp4: return raocp::cp4_name(c->f32, c->nx, c->nu);
+                case CpPath::Cp3: return "k_cp3<" + T + ", " + nn + (sh ? ", true> x2" : ", false>");
+                default: return kernel_name(c, 2) + " + " + kernel_name(c, 6);
+            }
+        }
         default: return "";
     }
 }
 
 // the end of a batch of `iters` iterations: the deferred test of its last iteration
 void enqueue_batch_tail(raocp_ctx* c, int iters) {
-    if (!defer_check(c)) return;
-    if (c->drc && c->sh_S == 0)
-        raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, drc_part(c, iters - 1), c->cp_rows,
-                                                       drc_nanbit(iters - 1), c->d_pub, err_word(c));
-    else
-        raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, c->redpart, c->cp_rows, 0, c->d_pub, err_word(c));
+    if (defer_check(c)) launch_cp_check(c, iters - 1, c->d_pub, err_word(c));
 }
-
 
 int set_ctl_alpha(raocp_ctx* c, double alpha) {
     HIPCHK(hipMemcpyAsync(&c->ctl->alpha, &alpha, sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return RAOCP_OK;
+}
+
+// what the context runs, from what was set up (raocp_path.h): at the end of raocp_ctx_create, and again at the
+// end of raocp_shard_setup, whose cut takes a shard off the forms that span the whole tree
+void resolve_ctx_paths(raocp_ctx* c) {
+    const raocp::PathCaps k{c->cp3, c->cp4, c->cp5,  c->cp6,  c->cp_v1,     c->dr,
+                            c->drc, c->dyn2, c->dyn3, c->dyn_split, c->cut > 0};  // PathCaps' order
+    c->path = raocp::resolve_paths(k, c->sh_S > 0);
 }
 
 void drop_graphs(raocp_ctx* c) {
@@ -1241,6 +1253,28 @@ int launch_batch(raocp_ctx* c, int iters) {
     return RAOCP_OK;
 }
 
+// the residual history of a finished run (rows 0 .. fk) into the caller's arrays
+int copy_hist(raocp_ctx* c, int fk, double* err_hist, double* delta_hist) {
+    std::vector<double> h((size_t)(fk + 1) * 6);
+    HIPCHK(hipMemcpy(h.data(), c->hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k <= fk; ++k)
+        for (int q = 0; q < 3; ++q) {
+            if (err_hist) err_hist[k * 3 + q] = h[(size_t)k * 6 + q];
+            if (delta_hist) delta_hist[k * 3 + q] = h[(size_t)k * 6 + 3 + q];
+        }
+    return RAOCP_OK;
+}
+// random inputs (seed 1) in the staging buffers tmpP / tmpD (raocp_op_bench, raocp_op_bench_rot)
+int bench_inputs(raocp_ctx* c) {
+    std::vector<double> hz(c->P), he(c->D);
+    std::mt19937_64 gen(1);
+    std::normal_distribution<double> nd(0.0, 1.0);
+    for (auto& v : hz) v = nd(gen);
+    for (auto& v : he) v = nd(gen);
+    int rc = copy_in(c, c->tmpP, hz.data(), c->P, 0);
+    return rc ? rc : copy_in(c, c->tmpD, he.data(), c->D, 0);
+}
+
 }  // namespace
 
 #include "raocp_setup.h"
@@ -1332,6 +1366,7 @@ int raocp_ctx_create(const raocp_tree_desc* t, const raocp_problem_desc* pr, int
     c->no_defer_check = !env_flag("RAOCP_DEFER_CHECK", true);
     c->drp.zpage = c->dev.zpage;
     c->drp.x0 = c->x0;
+    resolve_ctx_paths(c);
     *out = c;
     return RAOCP_OK;
 }
@@ -1700,13 +1735,7 @@ int raocp_cp_run(raocp_ctx* c, const double* x0, int max_iters, double tol, doub
         }
     }
     const int fk = c->h_ctl->final_k;
-    std::vector<double> h((size_t)(fk + 1) * 6);
-    HIPCHK(hipMemcpy(h.data(), c->hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int k = 0; k <= fk; ++k)
-        for (int q = 0; q < 3; ++q) {
-            if (err_hist) err_hist[k * 3 + q] = h[(size_t)k * 6 + q];
-            if (delta_hist) delta_hist[k * 3 + q] = h[(size_t)k * 6 + 3 + q];
-        }
+    if (int rh = copy_hist(c, fk, err_hist, delta_hist)) return rh;
     c->cur_z = c->Z[(fk + 1) % 3];
     c->cur_e = c->E[(fk + 1) % 2];
     if (iters) *iters = fk + 1;
@@ -2277,13 +2306,14 @@ int raocp_debug_dyn_stamps(raocp_ctx* c, unsigned long long* out, int cap) {
     DevGuard dg_(c);
     SweepLock sl_(c);
     // the regular-tree sweeps' stamps need only their own unit built with them (VAR_UNIT=dynr)
-    if (!raocp::kDiag && !(c && c->dr && raocp::dr_diag_build()))
+    const bool dr = c && c->path.dyn == DynPath::Dr;
+    if (!raocp::kDiag && !(dr && raocp::dr_diag_build()))
         return fail(RAOCP_ERR_ARG, "in-kernel stamps need a diagnostic build (make DIAG=1)");
     if (c && c->f32) return fail(RAOCP_ERR_ARG, "not available on an fp32 context (the CP loop and L / L^T are)");
     if (!c || !out || cap <= 0) return fail(RAOCP_ERR_ARG, "bad argument");
     // k_dr / k_drc stamp 4 slots per workgroup from slot 1024 (raocp_dynr.hip wg_stamp) and
     // k_drc's CP waves 128 slots from 3072
-    if (c->dr && (size_t)cap < std::max(c->drc ? (size_t)3072 + 128 : (size_t)0, 1024 + 4 * ((size_t)c->drp.nblk + 1)))
+    if (dr && (size_t)cap < std::max(c->path.fused ? (size_t)3072 + 128 : (size_t)0, 1024 + 4 * ((size_t)c->drp.nblk + 1)))
         return fail(RAOCP_ERR_ARG, "stamp buffer too small for the regular-tree sweep's workgroup stamps");
     // the tiered sweep stamps 64 slots per launch (2 per tier + the top)
     if (c->cut > 0 && (size_t)cap < 64 * (2 * c->tiers.size() + 1))
@@ -2299,29 +2329,26 @@ int raocp_debug_dyn_stamps(raocp_ctx* c, unsigned long long* out, int cap) {
     // workgroup / task that records (the number after it, e.g. "c200")
     const char* which = getenv("RAOCP_STAMP_KERNEL");
     if (which && which[0]) c->dev.cp_dbg = atoi(which + 1);
-    if (which && which[0] == 'p') {  // k_cpp on a valid control block (diagnostics)
+    const char w = which ? which[0] : 0;
+    if (w == 'c' && !raocp::cp_fused(c->path.cp)) return fail(RAOCP_ERR_ARG, "no fused CP kernel on this context");
+    if (w == 'f' && !c->path.fused) return fail(RAOCP_ERR_ARG, "no fused dynamics + CP launch on this context");
+    if (w == 'p' || w == 'c' || w == 'f') {  // the CP kernels run on a valid control block
         std::vector<double> x0(c->nx, 0.0);
         int rc2 = cp_init(c, x0.data(), 1 << 30, 0.0, 0.5);
         if (rc2) return rc2;
+    }
+    if (w == 'p') {  // k_cpp (diagnostics)
         launch_cpp(c);
-    } else if (which && which[0] == 'c') {  // the fused CP kernel (k_cp4 / k_cp3) on a valid control block
-        if (!c->cp3) return fail(RAOCP_ERR_ARG, "no fused CP kernel on this context");
-        std::vector<double> x0(c->nx, 0.0);
-        int rc2 = cp_init(c, x0.data(), 1 << 30, 0.0, 0.5);
-        if (rc2) return rc2;
-        launch_cp3(c);
-    } else if (which && which[0] == 'f') {  // the fused dynamics + CP launch (k_drc) on a valid control block
-        if (!c->drc) return fail(RAOCP_ERR_ARG, "no fused dynamics + CP launch on this context");
-        std::vector<double> x0(c->nx, 0.0);
-        int rc2 = cp_init(c, x0.data(), 1 << 30, 0.0, 0.5);
-        if (rc2) return rc2;
+    } else if (w == 'c') {  // the fused CP kernel (k_cp6 / k_cp5 / k_cp4 / k_cp3)
+        launch_cp_fused(c);
+    } else if (w == 'f') {  // the fused dynamics + CP launch (k_drc)
         const raocp::Bufs keep = c->bufs;
         c->bufs = rotated(c, 0);
         launch_drc(c, 0, false);
         c->bufs = keep;
-    } else if (which && which[0] == 'l') {  // k_ell on the staging buffers
+    } else if (w == 'l') {  // k_ell on the staging buffers
         launch_ell(c, c->tmpP, c->tmpD);
-    } else if (which && which[0] == 't') {  // k_ell_t
+    } else if (w == 't') {  // k_ell_t
         launch_ell_t(c, c->tmpD, c->tmpP);
     } else {
         launch_dynamics(c, solo, 0, nullptr);
@@ -2336,14 +2363,15 @@ int raocp_debug_dyn_stamps(raocp_ctx* c, unsigned long long* out, int cap) {
 // ---- subtree sharding ---------------------------------------------------------------
 int raocp_shard_setup(raocp_ctx* c, int nranks, int rank) {
     DevGuard dg_(c);
-    if (c && c->f32 && !c->dyn3)
+    const bool dyn3 = c && c->path.dyn == DynPath::Dyn3;  // k_dy3 is a context's sweep sharded or not
+    if (c && c->f32 && !dyn3)
         return fail(RAOCP_ERR_ARG, "fp32 sharding needs the per-stage streaming dynamics (uniform branching and slots)");
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return fail(RAOCP_ERR_ARG, "bad shard arguments");
     // one shard is the unsharded solve, unless forced (tests run the exchange path with R = 1)
     if (nranks == 1 && !getenv("RAOCP_SHARD_FORCE")) return RAOCP_OK;
     const int N = c->N;
     int S = c->cut;
-    if (c->dyn3) {
+    if (dyn3) {
         // the per-stage sweep: cut at the first stage with at least 8 subtrees per shard (the
         // replicated top above it is a few hundred nodes at most)
         S = 0;
@@ -2387,11 +2415,11 @@ int raocp_shard_setup(raocp_ctx* c, int nranks, int rank) {
         }
     }
     c->tier_own.clear();
-    if (!c->dyn3)
+    if (!dyn3)
         for (const auto& tp : c->tiers)
             c->tier_own.push_back({c->own_lo[tp.s0] - c->stage_ptr[tp.s0], c->own_hi[tp.s0] - c->own_lo[tp.s0]});
     c->d3own = c->d3st;
-    for (int t = S; t < N && c->dyn3; ++t) {
+    for (int t = S; t < N && dyn3; ++t) {
         c->d3own[t].i0 = c->own_lo[t];
         c->d3own[t].i1 = c->own_hi[t];
     }
@@ -2403,14 +2431,16 @@ int raocp_shard_setup(raocp_ctx* c, int nranks, int rank) {
     std::vector<std::pair<int, int>> lr_{{c->own_lo[N], c->own_hi[N]}};
     int rc;
     if ((rc = build_cp_blocks(c, pr_, lr_))) return rc;
+    // the fused forms' task lists (for every form that was set up). The first launch's parent ranges: the
+    // owned leaf parents, the owned families above them and the replicated top above the cut's parents
+    std::vector<std::pair<int, int>> ra;
+    if (N - 1 >= S) ra.push_back({c->own_lo[N - 1], c->own_hi[N - 1]});
+    for (int t = S; t < N - 1; ++t) ra.push_back({c->own_lo[t], c->own_hi[t]});
+    if (S >= 2) ra.push_back({0, c->stage_ptr[S - 1]});
     if (c->cp3) {
         // k_cp3 in two launches: the owned families and leaves plus the replicated top above
         // the cut's parents (storing its roots' xi2 for X1), then the cut's parents with the
         // roots' eta2 entries from X1
-        std::vector<std::pair<int, int>> ra;
-        if (N - 1 >= S) ra.push_back({c->own_lo[N - 1], c->own_hi[N - 1]});
-        for (int t = S; t < N - 1; ++t) ra.push_back({c->own_lo[t], c->own_hi[t]});
-        if (S >= 2) ra.push_back({0, c->stage_ptr[S - 1]});
         const long ta = cp3_tasks(c->cp3_ta, ra, c->own_lo[N], c->cp3_split ? c->own_hi[N] : c->own_lo[N], c->cp3_split,
                                   c->cp3_mL);
         c->cp3_ta.xlo = c->own_first;
@@ -2432,10 +2462,6 @@ int raocp_shard_setup(raocp_ctx* c, int nranks, int rank) {
         // X1 (the roots' s of the half step) the cut's parents' family tiles alone
         std::vector<std::pair<int, int>> er{{0, c->stage_ptr[S]}};
         for (int t = S; t < N; ++t) er.push_back({c->own_lo[t], c->own_hi[t]});
-        std::vector<std::pair<int, int>> ra;
-        if (N - 1 >= S) ra.push_back({c->own_lo[N - 1], c->own_hi[N - 1]});
-        for (int t = S; t < N - 1; ++t) ra.push_back({c->own_lo[t], c->own_hi[t]});
-        if (S >= 2) ra.push_back({0, c->stage_ptr[S - 1]});
         if (cp3_tasks(c->cp5_et, er, 0, 0, 1, 0, 64) < 0 || cp3_tasks(c->cp5_tk, ra, 0, 0, 1, c->cp3_mL) < 0 ||
             cp3_tasks(c->cp5_tkb, {{c->stage_ptr[S - 1], c->stage_ptr[S]}}, 0, 0, 1, c->cp3_mL) < 0)
             return fail(RAOCP_ERR_ARG, "shard's k_cp5 task lists exceed their " + std::to_string(raocp::kCp3MaxR) +
@@ -2452,6 +2478,7 @@ int raocp_shard_setup(raocp_ctx* c, int nranks, int rank) {
         (rc = c->alloc(&c->x1_send, (size_t)2 * xmax + 16)) || (rc = c->alloc(&c->x1_recv, (size_t)nranks * (2 * xmax + 16))) ||
         (rc = c->alloc(&c->red8, 16)) || (rc = c->upload_vec(&c->d_slc, slc)))
         return rc;
+    resolve_ctx_paths(c);  // sh_S > 0 now: the whole-tree forms are off
     drop_graphs(c);
     return RAOCP_OK;
 }
@@ -2520,8 +2547,7 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
         for (int r = 0; r < R; ++r) {
             raocp_ctx* c = cs[r];
             c->bufs = rotated(c, k % 6);
-            launch_dynamics(c, c->bufs, 1, c->ctl, 1);
-            shard_pack_x2(c);
+            shard_phase_back(c);
         }
         if ((rc = sync_all())) return rc;
         for (int r = 0; r < R; ++r) {
@@ -2529,11 +2555,7 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
             for (int q = 0; q < R; ++q)
                 HIPCHK(hipMemcpyAsync((char*)c->x2_recv + (size_t)q * x2_bytes(c), cs[q]->x2_send, x2_bytes(c),
                                       hipMemcpyDeviceToDevice, c->stream));
-            shard_unpack_x2(c);
-            launch_dynamics(c, c->bufs, 1, c->ctl, 2);
-            if (c->cp3) launch_cp3(c, 0);
-            else launch_cpd(c);
-            shard_pack_x1(c);
+            shard_phase_fwd(c);
         }
         if ((rc = sync_all())) return rc;
         for (int r = 0; r < R; ++r) {
@@ -2541,10 +2563,7 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
             for (int q = 0; q < R; ++q)
                 HIPCHK(hipMemcpyAsync(c->x1_recv + (size_t)q * x1_len(c), cs[q]->x1_send, (size_t)x1_len(c) * sizeof(double),
                                       hipMemcpyDeviceToDevice, c->stream));
-            shard_unpack_x1(c);
-            if (c->cp3) launch_cp3(c, 1);
-            else launch_cpp(c);
-            raocp::k_cp_reduce<<<1, kBlock, 0, c->stream>>>(c->ctl, c->redpart, c->cp_rows, c->red8);
+            shard_phase_top(c);
             HIPCHK(hipMemcpyAsync(c->h_ctl, c->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
         }
         if ((rc = sync_all())) return rc;
@@ -2554,13 +2573,7 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
     for (int r = 0; r < R; ++r) cs[r]->bufs = raocp::Bufs{cs[r]->Z[0], cs[r]->Z[1], cs[r]->Z[2], cs[r]->E[0], cs[r]->E[1]};
     raocp_ctx* c = cs[0];
     const int fk = c->h_ctl->final_k;
-    std::vector<double> h((size_t)(fk + 1) * 6);
-    HIPCHK(hipMemcpy(h.data(), c->hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int k = 0; k <= fk; ++k)
-        for (int q = 0; q < 3; ++q) {
-            if (err_hist) err_hist[k * 3 + q] = h[(size_t)k * 6 + q];
-            if (delta_hist) delta_hist[k * 3 + q] = h[(size_t)k * 6 + 3 + q];
-        }
+    if (int rh = copy_hist(c, fk, err_hist, delta_hist)) return rh;
     for (int r = 0; r < R; ++r) {
         cs[r]->cur_z = cs[r]->Z[(fk + 1) % 3];
         cs[r]->cur_e = cs[r]->E[(fk + 1) % 2];
@@ -2577,13 +2590,7 @@ int raocp_op_bench(raocp_ctx* c, int op, int reps, float* ms_per_launch) {
     SweepLock sl_(c);
     if (!c || reps < 1 || !ms_per_launch) return fail(RAOCP_ERR_ARG, "bad argument");
     // random inputs (seed 1), resident in HBM
-    std::vector<double> hz(c->P), he(c->D);
-    std::mt19937_64 gen(1);
-    std::normal_distribution<double> nd(0.0, 1.0);
-    for (auto& v : hz) v = nd(gen);
-    for (auto& v : he) v = nd(gen);
-    int rci;
-    if ((rci = copy_in(c, c->tmpP, hz.data(), c->P, 0)) || (rci = copy_in(c, c->tmpD, he.data(), c->D, 0))) return rci;
+    if (int rci = bench_inputs(c)) return rci;
     HIPCHK(hipStreamSynchronize(c->stream));
     double* outP = c->Z[2];
     double* outD = c->E[1];
@@ -2607,14 +2614,7 @@ int raocp_op_bench(raocp_ctx* c, int op, int reps, float* ms_per_launch) {
             case 6: launch_cpp(c); break;
             case 7: case 8: launch_cp_primal(c, true, op - 6); break;
             case 9: launch_dynamics(c, c->bufs, 1, c->ctl); break;
-            case 10:  // the CP iteration's kernels after the dynamics
-                if (c->cp3) {
-                    launch_cp3(c);
-                } else {
-                    launch_cpd(c);
-                    launch_cpp(c);
-                }
-                break;
+            case 10: launch_cp_after_sweep(c); break;  // the CP iteration's kernels after the dynamics
             case 11: launch_drc(c, 0, false); break;  // the fused dynamics + CP launch (k_drc)
             default: raocp::k_cp_check<<<1, kBlock, 0, c->stream>>>(c->ctl, c->hist, c->redpart, c->cp_rows, 0, nullptr, nullptr);
         }
@@ -2659,13 +2659,7 @@ int raocp_op_bench_rot(raocp_ctx* c, int op, int reps, int nsets, float* ms_per_
     SweepLock sl_(c);
     if (!c || reps < 1 || nsets < 1 || nsets > 16 || !ms_per_launch || (op != 0 && op != 1))
         return fail(RAOCP_ERR_ARG, "bad argument");
-    std::vector<double> hz(c->P), he(c->D);
-    std::mt19937_64 gen(1);
-    std::normal_distribution<double> nd(0.0, 1.0);
-    for (auto& v : hz) v = nd(gen);
-    for (auto& v : he) v = nd(gen);
-    int rci;
-    if ((rci = copy_in(c, c->tmpP, hz.data(), c->P, 0)) || (rci = copy_in(c, c->tmpD, he.data(), c->D, 0))) return rci;
+    if (int rci = bench_inputs(c)) return rci;
     std::vector<void*> mem;
     auto release = [&]() {
         for (void* q : mem) (void)hipFree(q);

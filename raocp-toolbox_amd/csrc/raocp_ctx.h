@@ -3,7 +3,11 @@
 // readers. Included by raocp_capi.hip only, after the kernel headers.
 #pragma once
 
+#include "raocp_path.h"
+
 using raocp::Ctl;
+using raocp::CpPath;
+using raocp::DynPath;
 using raocp::Dev;
 using raocp::kBlock;
 
@@ -151,6 +155,7 @@ struct raocp_ctx {
     double* part = nullptr;      // dot-product partials
     double* scal = nullptr;      // device scalars
     int cut = 0;                 // dynamics cut stage (0: per-stage kernels)
+    raocp::Paths path{};         // what runs (raocp_path.h): resolve_ctx_paths, from the flags that say "was set up"
     double* redpart = nullptr;   // per-block residual maxima [red_rows][6]
     int red_rows = 0;
     size_t lds_top = 0;
