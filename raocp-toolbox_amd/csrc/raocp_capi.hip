@@ -168,6 +168,15 @@ bool launch_ell3(raocp_ctx* c, const double* z, double* eta) {
     else return false;
     return true;
 }
+// k_ell2 / k_ellt2 hold one sqrtQ, sqrtR and sqrtPf fragment per node block; a block whose nodes use
+// different tables (a cost per mode) has no table index, so an fp32 context refuses L / L^T there
+// (its CP loop runs k_cpd / k_cpp<float>, which read a table per child)
+int ell_available(const raocp_ctx* c) {
+    if (c->f32 && c->ell2_mixed)
+        return fail(RAOCP_ERR_ARG, "fp32 L / L^T need one weight table per node block (this problem has a cost per mode); "
+                                   "the CP loop is available, with a step size from an fp64 context");
+    return RAOCP_OK;
+}
 void launch_ell(raocp_ctx* c, const double* z, double* eta) {
     if (c->ell3 && (c->f32 ? launch_ell3<float>(c, z, eta) : launch_ell3<double>(c, z, eta))) return;
     if (c->f32) dispatch_rt(c->nx, c->nu, Ell2Op<float>{}, c, z, eta, false);
@@ -1400,6 +1409,7 @@ int raocp_ell(raocp_ctx* c, const double* z, double* eta, int flags) {
     DevGuard dg_(c);
     if (!c || !z || !eta) return fail(RAOCP_ERR_ARG, "null argument");
     int rc;
+    if ((rc = ell_available(c))) return rc;
     if (flags & RAOCP_DEVICE_PTR) {
         launch_ell(c, z, eta);
         HIPCHK(hipGetLastError());
@@ -1416,6 +1426,7 @@ int raocp_ell_t(raocp_ctx* c, const double* eta, double* z, int flags) {
     DevGuard dg_(c);
     if (!c || !z || !eta) return fail(RAOCP_ERR_ARG, "null argument");
     int rc;
+    if ((rc = ell_available(c))) return rc;
     if (flags & RAOCP_DEVICE_PTR) {
         launch_ell_t(c, eta, z);
         HIPCHK(hipGetLastError());
@@ -1651,6 +1662,7 @@ static void dev_axpby(raocp_ctx* c, int nb, double a, const double* x, double b,
 int raocp_step_size(raocp_ctx* c, double* lambda_max, int max_it, double rtol) {
     DevGuard dg_(c);
     if (!c || !lambda_max) return fail(RAOCP_ERR_ARG, "null argument");
+    if (int ra = ell_available(c)) return ra;
     if (max_it <= 0) max_it = 300;
     if (rtol <= 0) rtol = 1e-14;
     const int P = (int)c->P;
@@ -2589,6 +2601,8 @@ int raocp_op_bench(raocp_ctx* c, int op, int reps, float* ms_per_launch) {
     DevGuard dg_(c);
     SweepLock sl_(c);
     if (!c || reps < 1 || !ms_per_launch) return fail(RAOCP_ERR_ARG, "bad argument");
+    if (op == 0 || op == 1)
+        if (int ra = ell_available(c)) return ra;
     // random inputs (seed 1), resident in HBM
     if (int rci = bench_inputs(c)) return rci;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2659,6 +2673,7 @@ int raocp_op_bench_rot(raocp_ctx* c, int op, int reps, int nsets, float* ms_per_
     SweepLock sl_(c);
     if (!c || reps < 1 || nsets < 1 || nsets > 16 || !ms_per_launch || (op != 0 && op != 1))
         return fail(RAOCP_ERR_ARG, "bad argument");
+    if (int ra = ell_available(c)) return ra;
     if (int rci = bench_inputs(c)) return rci;
     std::vector<void*> mem;
     auto release = [&]() {

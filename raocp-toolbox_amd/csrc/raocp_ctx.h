@@ -170,6 +170,7 @@ struct raocp_ctx {
     // MFMA CP kernels (raocp_cp2.hip): block shape, grid, LDS bytes; v1 = the scalar kernels
     int cp2_W = 4, cp2_FB = 1, cp2_LB = 16, cp2_nbF = 0, cp2_nbL = 0;
     size_t lds_cpd2 = 0, lds_cpp2 = 0;
+    bool ell2_mixed = false;     // a node block of the MFMA kernels mixes weight tables: no k_ell2 / k_ellt2<float>
     bool cp_v1 = false;          // RAOCP_CP_V1=1: the scalar k_cpd / k_cpp (raocp_cp.hip)
     // host copies the CP tables are (re)built from (build_cp_blocks)
     std::vector<int> h_yrel, h_chs, h_nch, h_pos7, h_pos14;

@@ -234,9 +234,9 @@ int build_cp_blocks(raocp_ctx* c, const std::vector<std::pair<int, int>>& prange
         for (int b = 0; b < c->cp2_nbF; ++b)
             if (fam2[raocp::kCpFamRecs * b].y > fam2[raocp::kCpFamRecs * b].x &&
                 (fam2[raocp::kCpFamRecs * b + 2].x < 0 || fam2[raocp::kCpFamRecs * b + 2].y < 0))
-                c->cp_v1 = true;
+                c->cp_v1 = c->ell2_mixed = true;
         for (int b = 0; b < c->cp2_nbL; ++b)
-            if (leaf2[raocp::kCpLeafRecs * b + 1].x < 0) c->cp_v1 = true;
+            if (leaf2[raocp::kCpLeafRecs * b + 1].x < 0) c->cp_v1 = c->ell2_mixed = true;
         c->lds_cpd2 = (size_t)nd2;
         c->lds_cpp2 = (size_t)np2;
         c->cp_rows = c->cp_v1 ? c->cp_nbF + c->cp_nbL : c->cp2_nbF + c->cp2_nbL;
@@ -536,6 +536,8 @@ int drc_setup(raocp_ctx* c, int n_cus) {
 int validate_tree(const raocp_tree_desc* t, int* N_out, int* cmax_out) {
     const int n = t->n, m = t->m, nx = t->nx, nu = t->nu;
     if (n < 2 || m < 1 || m >= n || nx < 1 || nu < 1) return fail(RAOCP_ERR_ARG, "bad tree sizes");
+    // the MFMA CP kernels are instantiated for up to 4 row tiles of nx and 2 of nu (dispatch_rt)
+    if (nx > 64 || nu > 32) return fail(RAOCP_ERR_ARG, "the CP kernels support nx <= 64 and nu <= 32");
     if (t->anc[0] != -1 || t->stage[0] != 0) return fail(RAOCP_ERR_TREE, "node 0 must be the root");
     for (int i = 1; i < n; ++i) {
         if (t->stage[i] < t->stage[i - 1]) return fail(RAOCP_ERR_TREE, "stage must be non-decreasing in node id");
@@ -1224,8 +1226,7 @@ int setup_cp_blocks(raocp_ctx* c, const raocp_tree_desc* t, const raocp_problem_
     c->cp_LB = LB;
     // MFMA CP kernels: W waves per block, one 16-node tile per wave and pass; W from the
     // tile count (about two blocks per CU), at least the lanes of a parent-row group
-    if (nx > 64 || nu > 32)
-        return fail(RAOCP_ERR_ARG, "the CP kernels support nx <= 64 and nu <= 32");
+    // (nx <= 64 and nu <= 32: validate_tree)
     {
         // four waves per block measured faster than one or two at configs 2 and 4 (the
         // per-block gather and barriers amortise over more tiles)

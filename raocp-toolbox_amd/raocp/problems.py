@@ -16,7 +16,7 @@ import raocp.core as core
 import raocp.core.constraints.rectangle as rectangle
 import raocp.core.dynamics as dynamics
 
-__all__ = ["recipe_main", "recipe_ops2x2", "recipe_cache3", "recipe_synthetic", "recipe_bin6",
+__all__ = ["recipe_main", "recipe_ops2x2", "recipe_cache3", "recipe_synthetic", "recipe_general", "recipe_general_small", "recipe_bin6",
            "recipe_c1n5", "recipe_config", "build_problem", "recipe_from_npz"]
 
 
@@ -67,6 +67,69 @@ def recipe_synthetic(P, v, N, tau, nx, nu, seed=0, alpha_r=0.9):
     return dict(P=P, v=v, N=N, tau=tau, A=A, B=B, Q=np.array([0.1 * np.eye(nx)] * M),
                 R=np.array([0.1 * np.eye(nu)] * M), Pf=0.01 * np.eye(nx), alpha_r=alpha_r,
                 nl_min=-np.ones(nx + nu), nl_max=np.ones(nx + nu), l_min=-np.ones(nx), l_max=np.ones(nx), x0=x0)
+
+
+def recipe_general(P, v, N, tau, nx, nu, seed=0, alpha_r=0.7, shared_weights=False):
+    """A problem no kernel can get right by luck: A, B and x0 as recipe_synthetic draws them (the
+    same stream, so the same values for a seed), then from a second stream default_rng([seed, 1])
+      - per mode k dense symmetric positive definite weights Q[k] = 0.1 (1 + k / 2) S(nx),
+        R[k] = 0.1 (1 + k / 4) S(nu) and Pf = 0.01 S(nx), S(n) = I + G G' / n with G standard
+        normal (a fresh G per matrix; condition number below 20, asserted), so every sqrtQ,
+        sqrtR and sqrtPf table is dense and the modes' tables differ;
+      - boxes with a bound of its own per entry, lo in [-1.5, -0.2] and hi in [0.1, 1.2], the
+        nonleaf box on [x; u] and the leaf box on x; every eighth entry (index 3, 11, ..) is
+        one-sided, lo = -inf and hi = +inf in turn (the leaf box starts with hi = +inf).
+    shared_weights: every mode takes mode 0's Q and R, for the kernels that need one weight
+    table over the whole tree (k_ell3 / k_ellt3 and the fused CP kernels)."""
+    rng = np.random.default_rng(seed)
+    M = P.shape[0]
+    A = np.zeros((M, nx, nx))
+    B = np.zeros((M, nx, nu))
+    for k in range(M):
+        A[k] = 0.1 * rng.standard_normal((nx, nx))
+        B[k] = 0.1 * rng.standard_normal((nx, nu))
+    x0 = rng.standard_normal(nx)
+    rng = np.random.default_rng([seed, 1])
+
+    def spd(n, c):
+        G = rng.standard_normal((n, n))
+        W = np.eye(n) + G @ G.T / n
+        W = c * 0.5 * (W + W.T)
+        assert np.linalg.cond(W) < 20.0
+        return W
+
+    Q = np.array([spd(nx, 0.1 * (1 + k / 2)) for k in range(M)])
+    R = np.array([spd(nu, 0.1 * (1 + k / 4)) for k in range(M)])
+    Pf = spd(nx, 0.01)
+    if shared_weights:
+        Q, R = np.array([Q[0]] * M), np.array([R[0]] * M)
+
+    def box(rows, first):
+        lo, hi = rng.uniform(-1.5, -0.2, rows), rng.uniform(0.1, 1.2, rows)
+        for q, e in enumerate(range(3, rows, 8)):
+            if (q + first) % 2 == 0:
+                lo[e] = -np.inf
+            else:
+                hi[e] = np.inf
+        return lo, hi
+
+    nl_min, nl_max = box(nx + nu, 0)
+    l_min, l_max = box(nx, 1)
+    return dict(P=P, v=v, N=N, tau=tau, A=A, B=B, Q=Q, R=R, Pf=Pf, alpha_r=alpha_r,
+                nl_min=nl_min, nl_max=nl_max, l_min=l_min, l_max=l_max, x0=x0)
+
+
+def recipe_general_small(name):
+    """The three small general problems the oracle is pinned on (tests/golden/general_kat.npz):
+    g53 on main.py's Markov chain (27 nodes), g175 and g618 on binary trees (15 and 7 nodes)."""
+    if name == "g53":
+        p = np.array([[0.1, 0.8, 0.1], [0.4, 0.6, 0.0], [0.0, 0.3, 0.7]])
+        return recipe_general(p, np.array([0.1, 0.6, 0.3]), 3, 3, 5, 3, seed=53, alpha_r=0.1)
+    if name == "g175":
+        return recipe_general(np.full((2, 2), .5), np.array([.5, .5]), 3, 3, 17, 5, seed=175, alpha_r=0.7)
+    if name == "g618":
+        return recipe_general(np.full((2, 2), .5), np.array([.5, .5]), 2, 2, 6, 18, seed=618, alpha_r=0.99)
+    raise ValueError(f"unknown general problem {name}")
 
 
 def recipe_bin6():

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from raocp.problems import build_problem, recipe_from_npz, recipe_synthetic
+from raocp.problems import build_problem, recipe_from_npz, recipe_general, recipe_synthetic
 from helpers import crafted_rotations, crafted_start
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -20,14 +20,20 @@ GOLDEN_FILE = {"main": "main_trace", "bin6": "traj_small", "c1n5": "traj_small"}
 # (census_violations; tests/test_branch_census.py asserts them for every start used). The
 # synthetic trees all take 1; the small cones of main (nx = 3) and c1n5 (nx = 4) leave a cone
 # kept at its random value near an edge more often, so fewer seeds qualify there.
+# The "-dense" trees have boxes of their own (a bound per entry, some one-sided), so a tree's
+# name is looked up before its base.
 SEED = 1
-SEEDS = {"main": 32, "c1n5": 5}
+SEEDS = {"main": 32, "c1n5": 5,
+         # the shape sweep's small cones (nx = 1, 5, 6): the smallest seed that qualifies
+         "s1x1": 82, "s1x1u": 82, "s5x3": 3, "s5x3u": 3, "s6x18": 3, "s6x18u": 3}
 # one start per instance of a batch
-BATCH_SEEDS = {"main": (32, 37, 50), "bin6": (1, 2, 3), "c1n5": (5, 12, 46), "m7x32": (1, 2, 3)}
+BATCH_SEEDS = {"main": (32, 37, 50), "bin6": (1, 2, 3), "c1n5": (5, 12, 46), "m7x32": (1, 2, 3),
+               "m7x32-dense": (1, 2, 3)}
 # the form of the batch kernel each problem reaches (kernel_info(13)), fp64 / fp32: the tables of the
 # golden problems fit the kernel's LDS budget and are staged there, those of m7x32 are read from HBM
 BATCH_KERNEL = {"main": ("k_cpb<true>", "k_cpb<float, true>"), "bin6": ("k_cpb<true>", "k_cpb<float, true>"),
-                "c1n5": ("k_cpb<true>", "k_cpb<float, true>"), "m7x32": ("k_cpb<false>", "k_cpb<float, false>")}
+                "c1n5": ("k_cpb<true>", "k_cpb<float, true>"), "m7x32": ("k_cpb<false>", "k_cpb<float, false>"),
+                "m7x32-dense": ("k_cpb<false>", "k_cpb<float, false>")}
 ENTRY_SEEDS = {"bin7": 1, "main": 22}  # the stand-alone entry points project the crafted dual itself
 T_OFFSET = 50.0
 ITERS = (0, 2)  # max_iters of the two runs of every case: one iteration, three iterations
@@ -59,7 +65,22 @@ def _seven_modes():
     return r
 
 
-# name -> recipe; "-nobox" drops every box, "-leafbox" the nonleaf ones
+def _dense(base, r):
+    """The tree, A, B and x0 of r with the weights and boxes of recipe_general: dense sqrtQ, sqrtR and
+    sqrtPf tables, a bound of its own per box entry, every eighth entry one-sided. Where the plain
+    tree has one cost over all modes so has this one (the streaming L / L^T and the fused CP
+    kernels take one weight table per tree; with a table per mode the library would, rightly, run
+    other kernels than the plain sibling's); where it has a cost per mode (m7x32) the dense
+    tables differ per mode too."""
+    shared = len({q.tobytes() for q in r["Q"]}) == 1 and len({q.tobytes() for q in r["R"]}) == 1
+    g = recipe_general(r["P"], r["v"], r["N"], r["tau"], r["A"].shape[1], r["B"].shape[2],
+                       seed=sum(map(ord, base)), alpha_r=r["alpha_r"], shared_weights=shared)
+    for k in ("Q", "R", "Pf", "nl_min", "nl_max", "l_min", "l_max"):
+        r[k] = g[k]
+    return r
+
+
+# name -> recipe; "-nobox" drops every box, "-leafbox" the nonleaf ones, "-dense": _dense
 _TREES = {
     "bin3": lambda: _synthetic(2, 3, 20, 8, 11),       # 15 nodes
     "bin4": lambda: _synthetic(2, 4, 20, 8, 22),       # 31 nodes
@@ -72,6 +93,31 @@ _TREES = {
     "quad64d3": lambda: _synthetic(4, 3, 64, 16, 7),   # 85 nodes
     "m7x32": _seven_modes,                             # 31 nodes, tables beyond the batch kernel's LDS
 }
+
+
+# ---- the shape sweep (tests/test_gpu_shapes.py): (nx, nu) -> branching, horizon and risk level of
+# its tree, 31 (binary, N = 4), 40 (ternary, N = 3) or 121 (ternary, N = 4) nodes, so that one
+# crafted start reaches every cone class on 30 % of the cones (helpers.crafted_rotations). Each shape
+# has two trees of recipe_general: "s<nx>x<nu>" with dense weight tables per mode (the node blocks
+# mix tables) and "s<nx>x<nu>u" with one dense table over the modes, which the MFMA CP kernels need.
+SHAPES = {(1, 1): (2, 4, 0.1), (5, 3): (3, 3, 0.7), (6, 18): (2, 4, 0.99), (16, 16): (2, 4, 0.1), (17, 5): (3, 3, 0.7),
+          (24, 17): (2, 4, 0.99), (33, 7): (3, 3, 0.1), (48, 32): (2, 4, 0.7), (49, 9): (3, 4, 0.99), (64, 32): (2, 4, 0.1)}
+
+
+def shape_tree(nx, nu, shared=False):
+    return f"s{nx}x{nu}" + ("u" if shared else "")
+
+
+def _shape_recipe(nx, nu, shared):
+    C, N, alpha_r = SHAPES[(nx, nu)]
+    P, v = _uniform(C)
+    return recipe_general(P, v, N, N, nx, nu, seed=100 * nx + nu, alpha_r=alpha_r, shared_weights=shared)
+
+
+for _nx, _nu in SHAPES:
+    for _sh in (False, True):
+        _TREES[shape_tree(_nx, _nu, _sh)] = functools.partial(_shape_recipe, _nx, _nu, _sh)
+SHAPE_TREES = tuple(shape_tree(nx, nu, sh) for nx, nu in SHAPES for sh in (False, True))
 
 
 @functools.lru_cache(maxsize=None)
@@ -87,7 +133,10 @@ def problem(tree):
     else:
         r = _TREES[base]()
         alpha = None
-    if variant in ("nobox", "leafbox"):
+    if variant == "dense":
+        assert base in _TREES, tree
+        r = _dense(base, r)
+    elif variant in ("nobox", "leafbox"):
         r["nl_min"] = r["nl_max"] = None
         if variant == "nobox":
             r["l_min"] = r["l_max"] = None
@@ -101,7 +150,7 @@ def problem(tree):
 
 
 def seed_of(tree):
-    return SEEDS.get(tree.partition("-")[0], SEED)
+    return SEEDS.get(tree, SEEDS.get(tree.partition("-")[0], SEED))
 
 
 def rotations(tree):
@@ -267,6 +316,12 @@ FAMILIES = [
     ("f32-cp3-quad64d3", "quad64d3", {"RAOCP_CP5": "0"}, "float32", [(10, "starts", "k_cp3<float, 64, 16")]),
     ("f32-cp3-bin7", "bin7", {}, "float32", [(10, "starts", "k_cp3<float, 20, 8")]),
 ]
+# the same kernels on the "-dense" tree of the same name: each keeps its plain sibling's
+# environment, dtype and kernel_info strings
+DENSE = ("drc-bin4", "drc-bin8", "cp6-bin7", "cp4-bin7", "cp3-bin7-split1", "cp3-bin32d5", "mfma-bin7", "scalar-bin7",
+         "cp5-quad20d4", "cp5-tern32d4", "f32-cp5-quad64d3", "f32-cp3-bin7")
+FAMILIES += [(c[0] + "-dense", c[1] + "-dense") + c[2:] for c in FAMILIES if c[0] in DENSE]
+assert len(FAMILIES) == 28 + len(DENSE)
 FAMILY = {c[0]: c for c in FAMILIES}
 
 # kernels that claim to share arithmetic, and the bound the suite already holds them to
@@ -276,10 +331,13 @@ AGREE = [
     ("cp6-bin7", "cp4-bin7", 1e-12), ("cp6-bin7", "cp3-bin7-split1", 1e-12), ("cp3-bin7-split1", "cp3-bin7-split0", 1e-12),
     ("cp5-quad20d4", "cp3-quad20d4", 1e-12), ("cp5-tern32d4", "cp3-tern32d4", 1e-12),
     ("mfma-bin7", "cp3-bin7-split1", 1e-10),
+    ("cp6-bin7-dense", "cp4-bin7-dense", 1e-12), ("cp6-bin7-dense", "cp3-bin7-split1-dense", 1e-12),
+    ("mfma-bin7-dense", "cp3-bin7-split1-dense", 1e-10),
 ]
 
 BATCH_TREES = tuple(BATCH_SEEDS)
 ENTRY_TREES = tuple(ENTRY_SEEDS)
 
 # every (tree, seed) some CP loop on the GPU starts from: the census test covers them all
-CENSUS_CASES = sorted({(c[1], seed_of(c[1])) for c in FAMILIES} | {(t, s) for t in BATCH_TREES for s in BATCH_SEEDS[t]})
+CENSUS_CASES = sorted({(c[1], seed_of(c[1])) for c in FAMILIES} | {(t, s) for t in BATCH_TREES for s in BATCH_SEEDS[t]} |
+                      {(t, seed_of(t)) for t in SHAPE_TREES})

@@ -7,6 +7,7 @@ fixtures the test-suite and the oracle are pinned against.
 
     python -B tests/golden/gen_golden.py            # writes tests/golden/*.npz
     python -B tests/golden/gen_golden.py warm       # only warm_start.npz
+    python -B tests/golden/gen_golden.py general    # only general_kat.npz
 
 The reference needs `turtle` (tkinter) and `tikzplotlib`, both absent here:
 they are stubbed as empty modules (scenario_tree.py:4, solver.py:8 import them
@@ -102,6 +103,65 @@ def recipe_synthetic(P, v, N, tau, nx, nu, seed=0, alpha_r=0.9):
                 Q=np.array([0.1 * np.eye(nx)] * M), R=np.array([0.1 * np.eye(nu)] * M), Pf=0.01 * np.eye(nx),
                 alpha_r=alpha_r, nl_min=-np.ones(nx + nu), nl_max=np.ones(nx + nu),
                 l_min=-np.ones(nx), l_max=np.ones(nx), x0=x0)
+
+
+def recipe_general(P, v, N, tau, nx, nu, seed=0, alpha_r=0.7):
+    """raocp/problems.py recipe_general, restated (tests/test_oracle_golden.py holds the two
+    together): A, B, x0 as recipe_synthetic; from default_rng([seed, 1]) dense per-mode weights
+    c (I + G G' / n), boxes with a bound of its own per entry, every eighth entry one-sided."""
+    rng = np.random.default_rng(seed)
+    M = P.shape[0]
+    A = np.zeros((M, nx, nx))
+    B = np.zeros((M, nx, nu))
+    for k in range(M):
+        A[k] = 0.1 * rng.standard_normal((nx, nx))
+        B[k] = 0.1 * rng.standard_normal((nx, nu))
+    x0 = rng.standard_normal(nx)
+    rng = np.random.default_rng([seed, 1])
+
+    def spd(n, c):
+        G = rng.standard_normal((n, n))
+        W = np.eye(n) + G @ G.T / n
+        W = c * 0.5 * (W + W.T)
+        assert np.linalg.cond(W) < 20.0
+        return W
+
+    Q = np.array([spd(nx, 0.1 * (1 + k / 2)) for k in range(M)])
+    R = np.array([spd(nu, 0.1 * (1 + k / 4)) for k in range(M)])
+    Pf = spd(nx, 0.01)
+
+    def box(rows, first):
+        lo, hi = rng.uniform(-1.5, -0.2, rows), rng.uniform(0.1, 1.2, rows)
+        for q, e in enumerate(range(3, rows, 8)):
+            if (q + first) % 2 == 0:
+                lo[e] = -np.inf
+            else:
+                hi[e] = np.inf
+        return lo, hi
+
+    nl_min, nl_max = box(nx + nu, 0)
+    l_min, l_max = box(nx, 1)
+    return dict(P=P, v=v, N=N, tau=tau, A=A, B=B, Q=Q, R=R, Pf=Pf, alpha_r=alpha_r,
+                nl_min=nl_min, nl_max=nl_max, l_min=l_min, l_max=l_max, x0=x0)
+
+
+def recipe_g53():
+    """(5, 3) on main.py's Markov chain, N = 3: 27 nodes."""
+    p = np.array([[0.1, 0.8, 0.1], [0.4, 0.6, 0.0], [0.0, 0.3, 0.7]])
+    return recipe_general(p, np.array([0.1, 0.6, 0.3]), 3, 3, 5, 3, seed=53, alpha_r=0.1)
+
+
+def recipe_g175():
+    """(17, 5), binary, N = 3: 15 nodes."""
+    return recipe_general(np.full((2, 2), .5), np.array([.5, .5]), 3, 3, 17, 5, seed=175, alpha_r=0.7)
+
+
+def recipe_g618():
+    """(6, 18), binary, N = 2: 7 nodes."""
+    return recipe_general(np.full((2, 2), .5), np.array([.5, .5]), 2, 2, 6, 18, seed=618, alpha_r=0.99)
+
+
+GENERAL = (("g53", recipe_g53), ("g175", recipe_g175), ("g618", recipe_g618))
 
 
 def recipe_bin6():
@@ -211,9 +271,10 @@ def parse_tex_trace(path):
     return np.stack([s_[:, 1] for s_ in series], axis=1), it
 
 
-def gen_ops(out):
-    rng = np.random.default_rng(1)
-    for name, rf in (("main", recipe_main), ("ops2x2", recipe_ops2x2), ("bin6", recipe_bin6), ("c1n5", recipe_c1n5)):
+def gen_ops(out, cases=(("main", recipe_main), ("ops2x2", recipe_ops2x2), ("bin6", recipe_bin6), ("c1n5", recipe_c1n5)),
+            seed=1):
+    rng = np.random.default_rng(seed)
+    for name, rf in cases:
         r = rf()
         tree, prob = build_ref(r)
         cache = core.Cache(prob)
@@ -242,9 +303,10 @@ def gen_ops(out):
         print(f"ops {name}: n={tree.num_nodes} |P|={zf.size} |D|={ef.size}")
 
 
-def gen_prox(out):
-    rng = np.random.default_rng(2)
-    for name, rf in (("main", recipe_main), ("bin6", recipe_bin6), ("cache3", recipe_cache3), ("c1n5", recipe_c1n5)):
+def gen_prox(out, cases=(("main", recipe_main), ("bin6", recipe_bin6), ("cache3", recipe_cache3), ("c1n5", recipe_c1n5)),
+             seed=2):
+    rng = np.random.default_rng(seed)
+    for name, rf in cases:
         r = rf()
         tree, prob = build_ref(r)
         n, m = tree.num_nodes, tree.num_nonleaf_nodes
@@ -364,6 +426,17 @@ def gen_warm(out):
         ref_solver.eigs = orig
 
 
+def gen_general(out):
+    """Dense per-mode weights, boxes with a bound per entry (some one-sided) and risk levels 0.1 /
+    0.7 / 0.99 on three small problems: L and L^T, the projections, prox f and prox g* with
+    its steps on seeded random inputs, and 15 CP iterations (max_iters = 14, tol = 0) at the
+    reference's own step size, stored with the traces."""
+    gen_ops(out, GENERAL, seed=11)
+    gen_prox(out, GENERAL, seed=12)
+    for name, rf in GENERAL:
+        run_chock(name, rf(), 14, 0.0, out)
+
+
 def gen_trees(out):
     rng = np.random.default_rng(5)
     p3 = np.array([[0.1, 0.8, 0.1], [0.4, 0.6, 0], [0, 0.3, 0.7]])
@@ -402,6 +475,11 @@ def main():
         w = {}
         gen_warm(w)
         np.savez_compressed(os.path.join(OUT, "warm_start.npz"), **w)
+        return
+    if sys.argv[1:] == ["general"]:  # only the general problems' fixture
+        g = {}
+        gen_general(g)
+        np.savez_compressed(os.path.join(OUT, "general_kat.npz"), **g)
         return
     ops = {}
     gen_ops(ops)

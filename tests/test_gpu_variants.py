@@ -72,7 +72,10 @@ def test_ell_t_block_kernel_matches_oracle(cfg):
     assert rel_err(blk.native.ell_t(ee), OracleProblem(prob).ell_t(ee)) <= 1e-12
 
 
-@pytest.mark.parametrize("cfg", ["chain", 2, "2-nobox", "2-leafbox", 4, "4-c2", "stop", "stop-nobox"])
+DENSE = {"dense20": (2, 20, 8), "dense32": (3, 32, 12), "dense64": (4, 64, 16)}  # branching, nx, nu of configs 2, 4, 5
+
+
+@pytest.mark.parametrize("cfg", ["chain", 2, "2-nobox", "2-leafbox", 4, "4-c2", "stop", "stop-nobox"] + list(DENSE))
 def test_ell_t_streaming_vs_block_and_oracle(cfg):
     """k_ellt3 (streaming wave tasks, uniform tables and branching C <= 4; raocp_ell3.hip)
     against k_ell_t (RAOCP_ELLT3=0) and the oracle (operators.py:55-94) on random duals:
@@ -81,10 +84,16 @@ def test_ell_t_streaming_vs_block_and_oracle(cfg):
     k_ell, operators.py:19-53), and both with the eta7 / eta14 offsets read from the tables
     (RAOCP_BOX_MODE=0) instead of computed from the all / none box patterns. "stop": a binary
     tree whose stopping time (4) is below the horizon (10), so the branching is not uniform:
-    k_ell3 takes its child-tile branch (eta7 from the flat tasks) and L^T runs k_ell_t."""
+    k_ell3 takes its child-tile branch (eta7 from the flat tasks) and L^T runs k_ell_t.
+    "dense20" / "dense32" / "dense64": the trees of configs 2, 4 and 5 cut down to N = 5 with one
+    dense sqrtQ, sqrtR and sqrtPf table (recipe_general), so that the off-diagonal entries of the
+    register-held weight fragments count; k_ell3 and k_ellt3 by name."""
     from oracle.raocp_oracle import OracleProblem
-    from raocp.problems import recipe_synthetic
-    if cfg == "chain":
+    from raocp.problems import recipe_general, recipe_synthetic
+    if cfg in DENSE:
+        C, nx, nu = DENSE[cfg]
+        r = recipe_general(np.full((C, C), 1 / C), np.full(C, 1 / C), 5, 5, nx, nu, seed=nx, shared_weights=True)
+    elif cfg == "chain":
         r = recipe_synthetic(np.ones((1, 1)), np.ones(1), 40, 40, 20, 8, seed=3)
     elif cfg == "4-c2":
         r = recipe_synthetic(np.full((2, 2), .5), np.full(2, .5), 9, 9, 32, 12, seed=4)
@@ -102,6 +111,12 @@ def test_ell_t_streaming_vs_block_and_oracle(cfg):
     tree, prob = build_problem(r)
     stream = core.Cache(prob)
     block = _with_env({"RAOCP_ELLT3": "0"}, lambda: core.Cache(prob))
+    if cfg in DENSE:
+        assert stream.native.kernel_info(0) == "k_ell3<double, %d, %d>" % DENSE[cfg][1:]
+        assert stream.native.kernel_info(1).startswith("k_ellt3<double, %d, %d, " % DENSE[cfg][1:])
+        assert block.native.kernel_info(1) == "k_ell_t<%d, %d>" % DENSE[cfg][1:]
+        sq = stream.packed.sqrt_q[0]
+        assert stream.packed.sqrt_q.shape[0] == 1 and np.abs(sq - np.diag(np.diag(sq))).max() > 1e-3 * np.abs(sq).max()
     rng = np.random.default_rng(12)
     ee = rng.standard_normal(stream.dual_size)
     a, b = stream.native.ell_t(ee), block.native.ell_t(ee)

@@ -184,3 +184,86 @@ def test_oracle_warm_start_matches_reference(golden):
         assert trace_rel_err(err, z[key + "error"]) <= 1e-9
         assert trace_rel_err(derr, z[key + "delta_error"]) <= 1e-9
         assert rel_err(p0, z[key + "z"]) <= 1e-10 and rel_err(d0, z[key + "eta"]) <= 1e-10
+
+
+# ---------------------------------------------------------------- general problems
+# Dense per-mode weights, boxes with a bound of its own per entry (some one-sided) and risk
+# levels 0.1 / 0.7 / 0.99 (raocp.problems.recipe_general): the inputs tests/test_gpu_shapes.py and
+# the "-dense" families of tests/branch_cases.py hold the kernels to, so the oracle is pinned on
+# them first, at this file's bounds for the golden problems above.
+GENERAL = ["g53", "g175", "g618"]
+
+
+@pytest.mark.parametrize("name", GENERAL)
+def test_general_recipe_is_the_fixtures_and_is_general(golden, name):
+    """recipe_general (restated in gen_golden.py) gives the stored recipe bit for bit; every
+    weight table has off-diagonal entries and differs between the modes, no box is symmetric
+    or constant over its entries, and the larger boxes have a one-sided entry."""
+    from raocp.problems import recipe_general_small
+    z = golden("general_kat")
+    r, orc = _oracle(z, name)
+    mine = recipe_general_small(name)
+    for k, val in mine.items():
+        assert np.array_equal(np.asarray(val), np.asarray(r[k])), k
+    for tab in (orc.SQ, orc.SR, orc.SP):
+        for S in tab:
+            assert S.shape[0] == 1 or np.abs(S - np.diag(np.diag(S))).max() > 1e-3 * np.abs(S).max()
+            assert np.isrealobj(S) and np.linalg.cond(S @ S) < 20.0
+    assert len(orc.SQ) == len(orc.SR) == r["P"].shape[0] > 1 and not np.allclose(orc.SQ[0], orc.SQ[1])
+    for lo, hi in ((r["nl_min"], r["nl_max"]), (r["l_min"], r["l_max"])):
+        assert np.all(lo < hi) and not np.any(lo == -hi)
+        for b in (lo[np.isfinite(lo)], hi[np.isfinite(hi)]):
+            assert np.unique(b).size == b.size
+        assert np.isinf(lo).sum() + np.isinf(hi).sum() == len(range(3, lo.size, 8))
+    assert np.isinf(r["nl_min"]).any() and np.isinf(r["l_max"]).any()
+
+
+@pytest.mark.parametrize("name", GENERAL)
+def test_general_oracle_ell_matches_reference(golden, name):
+    z = golden("general_kat")
+    r, orc = _oracle(z, name)
+    assert orc.P == z[f"{name}/ops_z"].size and orc.D == z[f"{name}/ops_eta"].size
+    assert rel_err(orc.ell(z[f"{name}/ops_z"]), z[f"{name}/ops_Lz"]) <= 1e-13
+    assert rel_err(orc.ell_t(z[f"{name}/ops_eta"]), z[f"{name}/ops_LTeta"]) <= 1e-13
+    out_d = orc.ell(z[f"{name}/ops_z"], template=z[f"{name}/ops_tmpl_dual"])
+    assert rel_err(out_d, z[f"{name}/ops_ell_out"]) <= 1e-13
+    out_p = orc.ell_t(z[f"{name}/ops_eta"], template=z[f"{name}/ops_tmpl_primal"])
+    assert rel_err(out_p, z[f"{name}/ops_ellT_out"]) <= 1e-13
+
+
+@pytest.mark.parametrize("name", GENERAL)
+def test_general_oracle_prox_steps_match_reference(golden, name):
+    """The dynamics and kernel projections, prox f, prox g* and its steps (the nonleaf and leaf
+    projections with the one-sided boxes among them)."""
+    z = golden("general_kat")
+    r, orc = _oracle(z, name)
+    P, K, Abar = orc.offline_per_node()
+    assert rel_err(P, z[f"{name}/off_P"]) <= 1e-12 and rel_err(K[:orc.m], z[f"{name}/off_K"]) <= 1e-12
+    alpha = float(z[f"{name}/prox_alpha"])
+    zin, ein, x0 = z[f"{name}/prox_z"], z[f"{name}/prox_eta"], r["x0"]
+    assert rel_err(orc.project_on_dynamics(zin, x0), z[f"{name}/prox_dyn"]) <= 1e-11
+    assert rel_err(orc.project_on_kernel(zin), z[f"{name}/prox_kernel"]) <= 1e-12
+    assert rel_err(orc.prox_f(zin, alpha, x0), z[f"{name}/prox_f"]) <= 1e-11
+    assert rel_err(orc.modify_dual_add_halves(ein, alpha), z[f"{name}/prox_modify_halves"]) <= 1e-14
+    assert rel_err(orc.project_on_constraints_nonleaf(ein), z[f"{name}/prox_proj_nonleaf"]) <= 1e-14
+    assert rel_err(orc.project_on_constraints_leaf(ein), z[f"{name}/prox_proj_leaf"]) <= 1e-14
+    assert rel_err(orc.prox_gconj(ein, alpha), z[f"{name}/prox_gconj"]) <= 1e-13
+    # the random dual leaves the boxes on both sides, and through a one-sided entry
+    c = orc.branch_census(ein)
+    assert c["box_nl"].min() > 0 and c["box_l"].min() > 0
+
+
+@pytest.mark.parametrize("name", GENERAL)
+def test_general_oracle_trajectories(golden, name):
+    """15 CP iterations at the fixture's step size: traces and the final iterate."""
+    z = golden("general_kat")
+    r, orc = _oracle(z, name)
+    assert int(z[f"{name}/cp_max_iters"]) == 14
+    lam, _ = orc.step_size()
+    assert abs(lam - float(z[f"{name}/cp_lambda"])) <= 1e-10 * lam
+    st, err, derr, zf, ef, _ = orc.chock(r["x0"], 14, float(z[f"{name}/cp_tol"]), alpha=float(z[f"{name}/cp_alpha"]))
+    assert st == int(z[f"{name}/cp_status"]) and err.shape == (15, 3)
+    assert trace_rel_err(err, z[f"{name}/cp_error"]) <= 1e-8
+    assert trace_rel_err(derr, z[f"{name}/cp_delta_error"]) <= 1e-8
+    assert rel_err(zf, z[f"{name}/cp_z"]) <= 1e-9
+    assert rel_err(ef, z[f"{name}/cp_eta"]) <= 1e-9
