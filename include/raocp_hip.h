@@ -278,13 +278,17 @@ int raocp_debug_dyn_stamps(raocp_ctx* ctx, unsigned long long* stamps, int cap);
  * communicator (one process per GPU; the 128-byte id comes from raocp_comm_unique_id on
  * one rank); raocp_cp_run / raocp_cp_bench then run the sharded iteration.
  * raocp_group_cp_run runs the shards of one process (tests: shards sharing a device),
- * exchanging through device copies. raocp_shard_owned: owned id range per stage. */
+ * exchanging through device copies; raocp_group_cp_run_warm is the same loop with a warm flag
+ * (warm != 0: every shard continues from its own current primal / dual, as raocp_cp_run does;
+ * raocp_group_cp_run is the cold start, warm = 0). raocp_shard_owned: owned id range per stage. */
 int raocp_shard_setup(raocp_ctx* ctx, int nranks, int rank);
 int raocp_shard_owned(raocp_ctx* ctx, int32_t* stage_lo, int32_t* stage_hi, int cap);
 int raocp_comm_unique_id(unsigned char* id128);
 int raocp_comm_init(raocp_ctx* ctx, const unsigned char* id128, int nranks, int rank);
 int raocp_group_cp_run(raocp_ctx** ctxs, int nranks, const double* x0, int max_iters, double tol, double alpha,
                        int* status, int* iters, double* err_hist, double* delta_hist);
+int raocp_group_cp_run_warm(raocp_ctx** ctxs, int nranks, const double* x0, int max_iters, double tol, double alpha,
+                            int warm, int* status, int* iters, double* err_hist, double* delta_hist);
 
 #ifdef __cplusplus
 }

@@ -2533,8 +2533,11 @@ int raocp_comm_init(raocp_ctx* c, const unsigned char* id128, int nranks, int ra
 
 // Shards that share one process and one device (tests, and a host-driven transport):
 // the CP loop runs eagerly, the exchanges are device copies between the shards' buffers.
-int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, double tol, double alpha, int* status,
-                       int* iters, double* err_hist, double* delta_hist) {
+// warm: every shard starts from its own current primal / dual (raocp_set_primal / raocp_set_dual,
+// or the end of its last run), as raocp_cp_run does; the entries a shard does not own are whatever
+// it holds and stay so.
+int raocp_group_cp_run_warm(raocp_ctx** cs, int R, const double* x0, int max_iters, double tol, double alpha, int warm,
+                            int* status, int* iters, double* err_hist, double* delta_hist) {
     if (!cs || R < 1 || !x0) return fail(RAOCP_ERR_ARG, "null argument");
     DevGuard dg_(cs[0]);
     for (int r = 0; r < R; ++r)
@@ -2545,7 +2548,7 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
         HIPCHK(hipSetDevice(c->device));
         if ((rc = ensure_hist(c, (size_t)max_iters + 1))) return rc;
         if ((rc = raocp_set_initial_state(c, x0))) return rc;
-        if ((rc = cp_init(c, x0, max_iters, tol, alpha))) return rc;
+        if ((rc = cp_init(c, x0, max_iters, tol, alpha, warm != 0))) return rc;
     }
     auto sync_all = [&]() -> int {
         for (int r = 0; r < R; ++r) HIPCHK(hipStreamSynchronize(cs[r]->stream));
@@ -2595,6 +2598,11 @@ int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, d
     if (int fe = fuse_err(c)) return fe;
     if (c->h_ctl->flags & 1) return fail(RAOCP_ERR_NAN_IN_BOX, "Rectangle constraint - 'nan' value cannot be constrained");
     return RAOCP_OK;
+}
+
+int raocp_group_cp_run(raocp_ctx** cs, int R, const double* x0, int max_iters, double tol, double alpha, int* status,
+                       int* iters, double* err_hist, double* delta_hist) {
+    return raocp_group_cp_run_warm(cs, R, x0, max_iters, tol, alpha, 0, status, iters, err_hist, delta_hist);
 }
 
 int raocp_op_bench(raocp_ctx* c, int op, int reps, float* ms_per_launch) {

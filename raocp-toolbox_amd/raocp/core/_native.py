@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "raocp_dual_scale", "raocp_dual_add_halves", "raocp_dual_project", "raocp_dual_moreau",
     "raocp_device_synchronize", "raocp_debug_dyn_stamps",
     "raocp_shard_setup", "raocp_shard_owned", "raocp_comm_unique_id", "raocp_comm_init", "raocp_group_cp_run",
+    "raocp_group_cp_run_warm",
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
     "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs", "raocp_cp_batch_mpc",
 ]
@@ -116,6 +117,8 @@ def load_library():
         "raocp_comm_init": (c_int, [vp, vp, c_int, c_int]),
         "raocp_group_cp_run": (c_int, [vp, c_int, vp, c_int, c_double, c_double, ctypes.POINTER(c_int),
                                        ctypes.POINTER(c_int), vp, vp]),
+        "raocp_group_cp_run_warm": (c_int, [vp, c_int, vp, c_int, c_double, c_double, c_int, ctypes.POINTER(c_int),
+                                            ctypes.POINTER(c_int), vp, vp]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)
@@ -154,9 +157,11 @@ def comm_unique_id():
     return out.tobytes()
 
 
-def group_cp_run(contexts, x0, max_iters, tol, alpha):
+def group_cp_run(contexts, x0, max_iters, tol, alpha, warm=False):
     """CP loop over the shards of one process (contexts[r].shard(r, R) done), exchanging
-    through device copies. Returns (status, error_cache, delta_error_cache) like cp_run."""
+    through device copies. warm=False starts every shard from (x0 at node 0, zeros) / 0; warm=True
+    from its own current primal / dual (set_primal / set_dual), as cp_run does. Returns (status,
+    error_cache, delta_error_cache) like cp_run."""
     lib = load_library()
     R = len(contexts)
     arr = (ctypes.c_void_p * R)(*[c._h for c in contexts])
@@ -164,8 +169,9 @@ def group_cp_run(contexts, x0, max_iters, tol, alpha):
     err = np.zeros((max_iters + 1, 3))
     derr = np.zeros((max_iters + 1, 3))
     status, iters = ctypes.c_int(), ctypes.c_int()
-    rc = lib.raocp_group_cp_run(ctypes.cast(arr, ctypes.c_void_p), R, _ptr(x0), int(max_iters), float(tol), float(alpha),
-                                ctypes.byref(status), ctypes.byref(iters), _ptr(err), _ptr(derr))
+    rc = lib.raocp_group_cp_run_warm(ctypes.cast(arr, ctypes.c_void_p), R, _ptr(x0), int(max_iters), float(tol),
+                                     float(alpha), int(bool(warm)), ctypes.byref(status), ctypes.byref(iters), _ptr(err),
+                                     _ptr(derr))
     if rc != 0:
         raise RaocpError(lib.raocp_last_error().decode(errors="replace"))
     k = iters.value

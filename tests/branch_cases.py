@@ -184,12 +184,19 @@ def reference(tree, K, rot, seed, f32=False, x0_scale=1.0):
 
 
 @functools.lru_cache(maxsize=None)
-def census(tree, rot, seed):
-    """The oracle's branch census of iteration 1 from the crafted start."""
+def modified_dual(tree, rot, seed):
+    """The modified dual iteration 1 projects from the crafted start (read-only)."""
     r, prob, op, alpha = problem(tree)
     p0, d0, _, _ = start(tree, rot, seed)
     v = op.chock_modified_duals(r["x0"], 0, alpha, p0=p0, d0=d0)[0]
-    return op.branch_census(v)
+    v.setflags(write=False)
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def census(tree, rot, seed):
+    """The oracle's branch census of iteration 1 from the crafted start."""
+    return problem(tree)[2].branch_census(modified_dual(tree, rot, seed))
 
 
 # golden main's leaf box is +-7 on a state of order 1: a standard normal start cannot reach its lo
@@ -338,6 +345,169 @@ AGREE = [
 BATCH_TREES = tuple(BATCH_SEEDS)
 ENTRY_TREES = tuple(ENTRY_SEEDS)
 
+
+# ---- the sharded path (tests/test_gpu_shard_branches.py). A case: id, tree, the environment its
+# contexts are created under, dtype, what kernel_info must report for every shard ((op, "eq" |
+# "starts" | "has", text)), how raocp_shard_setup picks the cut stage ("tiers": the tier planner's
+# cut; "dyn3": the first stage with >= 8 R nodes) and the shard counts R: every one of 1 (under
+# RAOCP_SHARD_FORCE=1), 2, 3, 4, 8 that shard setup accepts on the tree. The tiered sweep cuts bin8
+# at stage 4 (16 roots: every R; R = 3 owns 5 / 5 / 6) and s64x32 at stage 1 (2 roots: R <= 2);
+# the per-stage sweep needs a stage before the leaves with 8 R nodes: quad20d4 (1, 4, 16, 64, 256)
+# every R, tern32d4 (1, 3, 9, 27, 81) R <= 3, quad64d3 (1, 4, 16, 64) R <= 2.
+_SH_PINS = {"RAOCP_DR": "0", "RAOCP_CP4": "0", "RAOCP_CP5": "0", "RAOCP_CP6": "0"}  # test_gpu_shard.py _kern_cache
+_TIERS_20 = (9, "has", "k_dyn_bottom_back<20, 8")
+_SH_CP3 = [_TIERS_20, (10, "eq", "k_cp3<double, 20, 8, true> x2")]
+_SH_MFMA = [_TIERS_20, (10, "eq", "k_cpd2<double, 2, 1> + k_cpp2<double, 2, 1>")]
+_DY3 = "k_dy3_top_back"
+SHARDED = [
+    ("sh-cp3-bin8", "bin8", _SH_PINS, "float64", _SH_CP3, "tiers", (1, 2, 3, 4, 8)),
+    ("sh-cp3-bin8-dense", "bin8-dense", _SH_PINS, "float64", _SH_CP3, "tiers", (1, 2, 3, 4, 8)),
+    ("sh-mfma-bin8", "bin8", dict(_SH_PINS, **_MFMA), "float64", _SH_MFMA, "tiers", (1, 2, 3, 4, 8)),
+    ("sh-mfma-bin8-dense", "bin8-dense", dict(_SH_PINS, **_MFMA), "float64", _SH_MFMA, "tiers", (1, 2, 3, 4, 8)),
+    # a table per mode: the node blocks of the scalar kernels mix tables (the MFMA ones need one table)
+    ("sh-scalar-s64x32", "s64x32", dict(_SH_PINS, RAOCP_CP3="0"), "float64",
+     [(9, "has", "k_dyn_bottom_back<0, 0"), (10, "eq", "k_cpd<double, 0, 0> + k_cpp<double, 0, 0>")], "tiers", (1, 2)),
+    ("sh-cp5-quad20d4", "quad20d4", {"RAOCP_DYN3": "1"}, "float64",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<double, 20, 4> x1 + k_cp5_fams<double, 20, 8, 4>"), (10, "has", "after X1")],
+     "dyn3", (1, 2, 3, 4, 8)),
+    ("sh-cp5-quad20d4-dense", "quad20d4-dense", {"RAOCP_DYN3": "1"}, "float64",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<double, 20, 4> x1 + k_cp5_fams<double, 20, 8, 4>"), (10, "has", "after X1")],
+     "dyn3", (1, 2, 3, 4, 8)),
+    ("sh-cp5-tern32d4", "tern32d4", {"RAOCP_DYN3": "1"}, "float64",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<double, 32, 3> x1 + k_cp5_fams<double, 32, 12, 3>"), (10, "has", "after X1")],
+     "dyn3", (1, 2, 3)),
+    ("sh-cp5-tern32d4-dense", "tern32d4-dense", {"RAOCP_DYN3": "1"}, "float64",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<double, 32, 3> x1 + k_cp5_fams<double, 32, 12, 3>"), (10, "has", "after X1")],
+     "dyn3", (1, 2, 3)),
+    ("sh-f32-cp5-quad64d3", "quad64d3", {}, "float32",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<float, 64, 4> x1 + k_cp5_fams<float, 64, 16, 4>"), (10, "has", "after X1")],
+     "dyn3", (1, 2)),
+    ("sh-f32-cp5-quad64d3-dense", "quad64d3-dense", {}, "float32",
+     [(9, "has", _DY3), (10, "starts", "k_cp5_leaf<float, 64, 4> x1 + k_cp5_fams<float, 64, 16, 4>"), (10, "has", "after X1")],
+     "dyn3", (1, 2)),
+    ("sh-f32-cp3-quad64d3", "quad64d3", {"RAOCP_CP5": "0"}, "float32",
+     [(9, "has", _DY3), (10, "eq", "k_cp3<float, 64, 16, true> x2")], "dyn3", (1, 2)),
+]
+SHARDED_CASE = {c[0]: c for c in SHARDED}
+SHARD_TREES = tuple(sorted({c[1] for c in SHARDED}))
+# Seeds of the sharded cases' crafted starts: the smallest that meets census_violations and
+# cut_census_violations at every cut stage the tree's cases use; the tree's own seed where that does.
+# bin8 (seed 1): the owned slices [10, 16) of R = 3 and [12, 16) of R = 4 hold only one sign of the
+# roots' eta2; s64x32 (seed 1): the four child cones of its two roots miss the zero class.
+SHARD_SEEDS = {"bin8": 5, "bin8-dense": 5, "s64x32": 7}
+
+
+def shard_seed_of(tree):
+    return SHARD_SEEDS.get(tree, seed_of(tree))
+
+
+N_CUS = 256  # the compute units the tier planner costs its plan for (MI355X)
+
+
+@functools.lru_cache(maxsize=None)
+def tier_cut(tree):
+    """The stage raocp_shard_setup cuts a tiered-sweep context of the tree at: c->cut, the tier
+    planner's choice, by the planner itself on the host (tests/tierplan/cut_host_main.cpp over
+    csrc/raocp_tierplan.h, host compiler) from the tree as raocp_ctx_create hands it over: the
+    classes of the packed problem per stage, the (A, B) kinds in order of first use and the (kind,
+    parent class) pairs numbered by class (raocp_setup.h, "child kinds" and "number pairs by parent
+    class"). 0: the planner found no tier below a top (shard setup refuses the tree)."""
+    import shutil
+    import subprocess
+    import tempfile
+    from raocp.core._pack import pack_problem
+    pk = pack_problem(problem(tree)[1])
+    n, m, N = int(pk.n), int(pk.m), int(pk.N)
+    stage_ptr = [int(np.searchsorted(pk.stage, t)) for t in range(N + 1)] + [n]
+    kinds, pairs = {}, {}
+    for j in range(1, n):
+        kid = kinds.setdefault((int(pk.i_a[j]), int(pk.i_b[j])), len(kinds))
+        pairs.setdefault((kid, int(pk.i_k[pk.anc[j]])), len(pairs))
+    nk = int(pk.n_classes)
+    by_class = sorted(c for _, c in pairs)  # the stable sort by parent class keeps the counts per class
+    pair_ptr = [int(np.searchsorted(by_class, c)) for c in range(nk)] + [len(pairs)]
+    cls_ptr = [int(np.searchsorted(pk.class_stage, t)) for t in range(N + 1)]
+    words = [N, n, len(kinds), int(pk.nx), int(pk.nu), N_CUS] + stage_ptr + [m] + [int(v) for v in pk.ch_start[:m]] + \
+        [int(v) for v in pk.nch[:m]] + cls_ptr + [nk] + pair_ptr
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "cut_host")
+        subprocess.run([cxx, "-std=c++17", "-O1", "-I", os.path.join(root, "raocp-toolbox_amd", "csrc"),
+                        os.path.join(root, "tests", "tierplan", "cut_host_main.cpp"), "-o", exe],
+                       check=True, capture_output=True, text=True, timeout=300)
+        out = subprocess.run([exe], input=" ".join(map(str, words)), check=True, capture_output=True, text=True, timeout=60).stdout
+    return int(out.split()[1])
+
+
+def shard_cut(tree, how, R):
+    """The cut stage of R shards of the tree on the host, by raocp_shard_setup's rule: the tier
+    planner's cut for the tiered sweep, the first stage before the leaves with >= 8 R nodes for
+    the per-stage sweep; None where shard setup refuses (no such stage, or fewer roots than shards)."""
+    op = problem(tree)[2]
+    width = np.bincount(op.stage)
+    if how == "tiers":
+        S = tier_cut(tree)
+        S = S if 0 < S < op.N else 0
+    else:
+        S = next((t for t in range(1, op.N) if width[t] >= 8 * R), 0)
+    return S if S and width[S] >= R else None
+
+
+def cut_census_violations(op, vs, S, Rs):
+    """The conditions a crafted start must meet at a cut stage S in iteration 1, where the code only
+    a shard runs sits (the cut's parents' second CP launch with the roots' eta2 entries from X1; the
+    roots' own families, whose eta2 travels), checked on the modified dual of each rotation (vs);
+    returns the list of those it misses:
+      - every SOC class among the child cones of the stage-S nodes, and among those of their
+        children (their leaf cones where the stage-S nodes' children are the leaves);
+      - both signs among the pre-clamp eta2 of the stage-S nodes, the entries that travel in X1;
+      - both a lo and a hi branch among the eta7 rows of the stage S - 1 parents, where boxed;
+      - for each R of Rs, a negative and a positive pre-clamp eta2 in every shard's owned slice of
+        stage S of >= 4 nodes (the slice rule of raocp_shard_setup).
+    The margins of census_violations (>= 0.1 on every cone of the tree) hold for these cones with it."""
+    from helpers import shard_ranges
+    bad = []
+    cens = [op.branch_census(v) for v in vs]
+    kid_stage = op.stage[op.kids]
+    groups = [("children of stage S", "child_class", kid_stage == S + 1)]
+    if S + 2 <= op.N:
+        groups.append(("grandchildren of stage S", "child_class", kid_stage == S + 2))
+    else:
+        groups.append(("leaf cones below stage S", "leaf_class", op.stage[op.leaves] == S + 1))
+    for what, key, sel in groups:
+        got = np.bincount(np.concatenate([c[key][sel] for c in cens]), minlength=3)
+        if got.min() == 0:
+            bad.append(f"S = {S}: cone classes of the {what} {got.tolist()}")
+    roots = np.flatnonzero(op.stage == S)
+    par = np.flatnonzero((op.stage[:op.m] == S - 1) & op.nl_active)
+    for q, v in enumerate(vs):
+        e2 = v[op.E2[roots]]
+        if not ((e2 > 0).any() and (e2 < 0).any()):
+            bad.append(f"S = {S} start {q}: eta2 of the roots has one sign")
+        if par.size:
+            w = v[op.E7[par][:, None] + np.arange(op.nx + op.nu)]
+            lo, hi = (w <= op.nl_lo[par]).sum(), ((w > op.nl_lo[par]) & (w >= op.nl_hi[par])).sum()
+            if not (lo and hi):
+                bad.append(f"S = {S} start {q}: eta7 of the cut's parents lo / hi {int(lo)} / {int(hi)}")
+        for R in Rs:
+            for k, (own_lo, own_hi) in enumerate(shard_ranges(op, S, R)):
+                e = v[op.E2[own_lo[S]:own_hi[S]]]
+                if e.size >= 4 and not ((e > 0).any() and (e < 0).any()):
+                    bad.append(f"S = {S} start {q}: eta2 of shard {k} of {R} has one sign")
+    return bad
+
+
+def shard_cuts(tree):
+    """{S: the R values cut there} over the sharded cases of a tree."""
+    out = {}
+    for c in SHARDED:
+        if c[1] == tree:
+            for R in c[6]:
+                out.setdefault(shard_cut(tree, c[5], R), set()).add(R)
+    return out
+
 # every (tree, seed) some CP loop on the GPU starts from: the census test covers them all
 CENSUS_CASES = sorted({(c[1], seed_of(c[1])) for c in FAMILIES} | {(t, s) for t in BATCH_TREES for s in BATCH_SEEDS[t]} |
-                      {(t, seed_of(t)) for t in SHAPE_TREES})
+                      {(t, seed_of(t)) for t in SHAPE_TREES} | {(t, shard_seed_of(t)) for t in SHARD_TREES})

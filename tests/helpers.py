@@ -80,6 +80,100 @@ def segment_rel_err(got, ref, op, kind=None):
     return out
 
 
+def shard_ranges(op, S, R):
+    """(own_lo, own_hi) per stage 0..N of each of R shards cut at stage S, on the host: what
+    raocp_shard_owned returns after raocp_shard_setup (raocp_capi.hip:2401-2428: shard r's roots are
+    stage S's ids [r nb / R, (r + 1) nb / R) in integer division, "owned id range per stage: the whole
+    stage above the cut, descendants below")."""
+    first = np.array([int(np.flatnonzero(op.stage == t)[0]) for t in range(op.N + 1)] + [op.n])
+    nb = int(first[S + 1] - first[S])
+    assert 1 <= S <= op.N and nb >= R >= 1, (S, nb, R)
+    out = []
+    for r in range(R):
+        lo, hi = int(first[S] + r * nb // R), int(first[S] + (r + 1) * nb // R)
+        own_lo, own_hi = list(first[:S]), list(first[1:S + 1])
+        for t in range(S, op.N + 1):
+            own_lo.append(lo)
+            own_hi.append(hi)
+            if t < op.N and hi > lo:
+                lo, hi = int(op.chs[lo]), int(op.chs[hi - 1] + op.nch[hi - 1])
+        out.append((np.array(own_lo, dtype=np.int64), np.array(own_hi, dtype=np.int64)))
+    return out
+
+
+def _node_entries(starts, sizes, nodes):
+    """Flat indices of the blocks [starts[i], starts[i] + sizes[i]) of the given nodes."""
+    starts, sizes = np.asarray(starts, np.int64)[nodes], np.asarray(sizes, np.int64)[nodes]
+    if starts.size == 0:
+        return np.zeros(0, np.int64)
+    return np.repeat(starts - np.concatenate([[0], np.cumsum(sizes)[:-1]]), sizes) + np.arange(sizes.sum())
+
+
+def shard_masks(op, own_lo, own_hi, S):
+    """(primal mask, dual mask) of the entries of the flat primal and dual a shard answers for after
+    a run, from its owned id range per stage (shard_owned) and its cut stage S.
+
+    The rule restates raocp_shard_setup (raocp_capi.hip:2412-2428): a shard holds every node of the
+    stages above the cut (own_lo / own_hi of a stage t < S are the whole stage) and, from the cut
+    down, the descendants of its own roots. An entry goes with the node whose work item computes it:
+      x, u, y, tau, s                  the node itself (u, y: nonleaf nodes);
+      eta1, eta2, eta7                 the node as parent (its family's dual rows);
+      eta3 .. eta6                     the node as child (its own cone);
+      eta11 .. eta14                   the node as leaf;
+    and only live slots count (OracleProblem.live_masks: the (1, 1) placeholders are nobody's).
+    At the cut the kernels keep more than this in every shard: the cut's parents' families run
+    replicated in the second CP launch (cp3_tb / cp5_tkb over [stage_ptr[S - 1], stage_ptr[S]),
+    raocp_capi.hip:2460, 2478), which writes tau, s and eta3 .. eta6 of every root, and X1 scatters
+    every root's eta2 (k_unpack_x1). Those copies are not claimed here: the owner's copy is the one
+    its own subtree reads, so each such entry is held to account exactly once, in its owner, and
+    below the top the masks of the shards are disjoint."""
+    own_lo, own_hi = np.asarray(own_lo, np.int64), np.asarray(own_hi, np.int64)
+    assert own_lo.size == own_hi.size == op.N + 1 and 1 <= S <= op.N
+    node = np.zeros(op.n, dtype=bool)
+    for a, b in zip(own_lo, own_hi):
+        node[a:b] = True
+    assert node[op.stage < S].all(), "the stages above the cut are replicated whole"
+    return _masks_of_nodes(op, node)
+
+
+def shard_top_masks(op, S):
+    """(primal mask, dual mask) of the part of shard_masks every shard holds a copy of: the entries
+    of the nodes of the stages above the cut, by the same rule."""
+    return _masks_of_nodes(op, op.stage < S)
+
+
+def _masks_of_nodes(op, sel):
+    ids = np.flatnonzero(sel)
+    par, kid, leaf = ids[ids < op.m], ids[ids >= 1], ids[ids >= op.m]
+    pm, dm = np.zeros(op.P, dtype=bool), np.zeros(op.D, dtype=bool)
+    for k, who in enumerate((ids, par, par, ids, ids)):
+        starts = np.concatenate([[0], np.cumsum(op.p_sizes[k])[:-1]]) + (op.X0, op.U0, op.Y0, op.T0, op.S0)[k]
+        pm[_node_entries(starts, op.p_sizes[k], who)] = True
+    for k, who in enumerate((par, par, kid, kid, kid, kid, par, leaf, leaf, leaf, leaf)):
+        dm[_node_entries(op.d_off[k], op.d_sizes[k], who)] = True
+    live_p, live_d = op.live_masks()
+    return pm & live_p, dm & live_d
+
+
+def masked_segment_rel_err(got, ref, op, kind, mask):
+    """segment_rel_err restricted to a mask: per segment, max |got - ref| over the segment's masked
+    entries / the segment's own largest |ref| entry (over the whole segment, as segment_rel_err
+    scales it, so the masked figure is held to the same bound)."""
+    got = np.asarray(got, dtype=float).reshape(-1)
+    ref = np.asarray(ref, dtype=float).reshape(-1)
+    assert got.shape == ref.shape == mask.shape and kind in ("primal", "dual")
+    if kind == "primal":
+        names, edges = PRIMAL_SEGMENTS, [op.X0, op.U0, op.Y0, op.T0, op.S0, op.P]
+    else:
+        names, edges = DUAL_SEGMENTS, [int(o[0]) for o in op.d_off] + [op.D]
+    out = {}
+    for k, name in enumerate(names):
+        sl = slice(edges[k], edges[k + 1])
+        a, b, w = got[sl], ref[sl], mask[sl]
+        out[name] = float(np.max(np.abs(a[w] - b[w])) / max(np.max(np.abs(b)), 1e-300)) if w.any() else 0.0
+    return out
+
+
 def trace_rel_err(a, b):
     a = np.atleast_2d(a)
     b = np.atleast_2d(b)

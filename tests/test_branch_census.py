@@ -203,3 +203,47 @@ def test_segment_rel_err_takes_the_kind_it_is_told():
     with pytest.raises(AssertionError):
         segment_rel_err(e, e, same)
     assert list(segment_rel_err(e, e, same, "primal")) == ["x", "u", "y", "tau", "s"]
+
+
+@pytest.mark.parametrize("tree", bc.SHARD_TREES)
+def test_crafted_start_takes_every_branch_at_the_cut(tree):
+    """The code only a shard runs sits at the cut stage S and at its parents; the tree-wide census
+    does not say where its classes fall. At every cut the sharded cases of the tree use (the tier
+    planner's cut on the host, or the first stage with 8 R nodes: branch_cases.shard_cut, which the
+    GPU test holds against raocp_shard_owned), iteration 1 from the sharded cases' start takes every
+    cone class among the child cones of the stage-S nodes and among those of their children, both
+    signs under the clamp of the roots' eta2 (the entries X1 carries) over the stage and within
+    every shard's slice of >= 4 roots, and a lo and a hi branch in the cut's parents' boxes
+    (branch_cases.cut_census_violations); the tree-wide conditions, margins included, hold for the
+    same seed (CENSUS_CASES)."""
+    r, prob, op, alpha = bc.problem(tree)
+    seed = bc.shard_seed_of(tree)
+    assert (tree, seed) in bc.CENSUS_CASES
+    cuts = bc.shard_cuts(tree)
+    assert cuts and None not in cuts, cuts
+    vs = [bc.modified_dual(tree, rot, seed) for rot in range(bc.rotations(tree))]
+    for S, Rs in sorted(cuts.items()):
+        print(tree, "seed", seed, "cut", S, "R", sorted(Rs))
+        assert bc.cut_census_violations(op, vs, S, sorted(Rs)) == []
+
+
+def test_sharded_table_meets_the_required_shard_counts():
+    """Every sharded case runs at least R = 2; the two-tier binary tree's rows include R = 3 (16
+    roots at the cut: 5 / 5 / 6); a ternary case includes R = 2; the R values listed are exactly
+    those of 1, 2, 3, 4, 8 the host rule of shard setup accepts."""
+    for cid, tree, env, dtype, info, how, Rs in bc.SHARDED:
+        assert 2 in Rs, cid
+        assert tuple(R for R in (1, 2, 3, 4, 8) if bc.shard_cut(tree, how, R) is not None) == Rs, cid
+        if tree.startswith("bin8"):
+            assert 3 in Rs and bc.shard_cut(tree, how, 3) == 4
+    assert any(c[1].startswith("tern") and 2 in c[6] for c in bc.SHARDED)
+
+
+def test_the_cut_conditions_reject_the_seed_they_replaced():
+    """What the sharded cases' own seeds are for: on bin8 the tree's seed leaves a shard's slice of
+    the roots with one sign of eta2, and a cold start misses the cone classes at the cut."""
+    r, prob, op, alpha = bc.problem("bin8")
+    v = bc.modified_dual("bin8", 0, bc.seed_of("bin8"))
+    assert any("one sign" in b for b in bc.cut_census_violations(op, [v], 4, [3, 4]))
+    cold = op.chock_modified_duals(r["x0"], 0, alpha)[0]
+    assert any("cone classes" in b for b in bc.cut_census_violations(op, [cold], 4, [2]))

@@ -344,3 +344,36 @@ def test_shard_slices_partition_the_roots():
             assert sl[0][0] == 100 and sum(c for _, c in sl) == nb
             assert all(sl[i][0] + sl[i][1] == sl[i + 1][0] for i in range(R - 1))
             assert max(c for _, c in sl) - min(c for _, c in sl) <= 1
+
+
+# ---------------------------------------------------------------------------------------
+# the entries each shard answers for (helpers.shard_masks, used by tests/test_gpu_shard_branches.py):
+# a GPU test that compares "the owned iterate" must not pass by leaving entries out
+# ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tree", ["bin8", "tern32d4"])  # binary, 511 nodes; ternary, 121 nodes
+def test_shard_masks_cover_every_live_entry_once(tree):
+    """For R = 1, 2, 3, 4, 8 and every cut stage with at least R nodes, with the owned ranges of the
+    slice rule: the union of the shards' masks is every live slot of the primal and of the dual
+    (the share left out is zero), no placeholder slot is in a mask, and outside the replicated top
+    the masks are disjoint (on it they all coincide)."""
+    sys.path[:0] = [p for p in (os.path.join(ROOT, "raocp-toolbox_amd"), os.path.join(ROOT, "tests")) if p not in sys.path]
+    import branch_cases as bc
+    from helpers import shard_masks, shard_ranges, shard_top_masks
+    op = bc.problem(tree)[2]
+    assert op.n == {"bin8": 511, "tern32d4": 121}[tree]
+    live_p, live_d = op.live_masks()
+    width = np.bincount(op.stage)
+    seen = 0
+    for R in (1, 2, 3, 4, 8):
+        for S in range(1, op.N + 1):
+            if width[S] < R:
+                continue
+            seen += 1
+            top_p, top_d = shard_top_masks(op, S)
+            masks = [shard_masks(op, lo, hi, S) for lo, hi in shard_ranges(op, S, R)]
+            for live, top, ms in ((live_p, top_p, [m[0] for m in masks]), (live_d, top_d, [m[1] for m in masks])):
+                count = np.sum(ms, axis=0)
+                assert np.array_equal(count > 0, live), (tree, R, S, int((live & (count == 0)).sum()), int((~live & (count > 0)).sum()))
+                assert np.array_equal(count[top], np.full(int(top.sum()), R)) and top.any()
+                assert (count[~top] <= 1).all(), (tree, R, S)
+    assert seen >= 15  # at least three stages of either tree take all five R
