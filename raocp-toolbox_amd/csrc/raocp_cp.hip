@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(kBlock) k_cpd(Dev p, Ctl* __restrict__ ctl, Bu
                     T ss = T(0);
                     for (int q = 0; q < G - 1; ++q) ss += s_x[base + q];
                     const T nf = sqrt(ss), t = s_x[base + G - 1];
-                    finish(e, dv, v, soc_apply_t<T>(v, r == G - 1, nf, t), bb);
+                    finish(e, dv, v, soc_apply<T>(v, r == G - 1, nf, t), bb);
                 }
                 __syncthreads();
             }
@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(kBlock) k_cpd(Dev p, Ctl* __restrict__ ctl, Bu
                     const T dv = D7[fr.w - e7a + rr];
                     const T v = (dv + alpha * av) / alpha;
                     const int bi = BI[ii];
-                    finish(e, dv, v, box_apply_t<T>(v, BL[bi * (nx + nu) + rr], BH[bi * (nx + nu) + rr], ctl), bb);
+                    finish(e, dv, v, box_apply<T>(v, BL[bi * (nx + nu) + rr], BH[bi * (nx + nu) + rr], ctl), bb);
                 }
             }
         }
@@ -289,10 +289,10 @@ __global__ void __launch_bounds__(kBlock) k_cpd(Dev p, Ctl* __restrict__ ctl, Bu
                 if (r < nx + 2) {
                     T ss = T(0);
                     for (int q = 0; q < nx + 1; ++q) ss += s_x[base + q];
-                    finish(e, dv, v, soc_apply_t<T>(v, r == nx + 1, sqrt(ss), s_x[base + nx + 1]), bb);
+                    finish(e, dv, v, soc_apply<T>(v, r == nx + 1, sqrt(ss), s_x[base + nx + 1]), bb);
                 } else {
                     const int rr = r - nx - 2;
-                    finish(e, dv, v, box_apply_t<T>(v, BL[lr.y * nx + rr], BH[lr.y * nx + rr], ctl), bb);
+                    finish(e, dv, v, box_apply<T>(v, BL[lr.y * nx + rr], BH[lr.y * nx + rr], ctl), bb);
                 }
             }
             __syncthreads();

@@ -31,37 +31,10 @@
 // Arithmetic (the reference's): L(2z+ - p) and L(z+ - p) are formed from A operands
 // 2z+ - p and z+ - p, not as 2Lz+ - Lp, so only the summation order differs from numpy.
 
-// ---- 16x16x4 MFMA in T -------------------------------------------------------------
-template <class T>
-struct MF;
-template <>
-struct MF<double> {
-    typedef double v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ v4 mma(double a, double b, v4 c) {
-        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-    }
-    // tile row (A row) of accumulator element e in lane group h = lane >> 4, and back
-    static __device__ __forceinline__ int row(int h, int e) { return h + 4 * e; }
-    static __device__ __forceinline__ int h_of(int a) { return a & 3; }
-    static __device__ __forceinline__ int e_of(int a) { return a >> 2; }
-};
-template <>
-struct MF<float> {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ v4 mma(float a, float b, v4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ int row(int h, int e) { return 4 * h + e; }
-    static __device__ __forceinline__ int h_of(int a) { return a >> 2; }
-    static __device__ __forceinline__ int e_of(int a) { return a & 3; }
-};
+// (MF, glbp / cglbp: raocp_tile.h; soc_apply, box_apply, block_max_store: raocp_cpops.h)
 
 template <class U>
 using ldsp = const __attribute__((address_space(3))) U*;
-template <class U>
-using glbp = __attribute__((address_space(1))) U*;
-template <class U>
-using cglbp = const __attribute__((address_space(1))) U*;
 
 // LDS-DMA staging of any element type: each region gets whole 16-B chunk slots starting
 // at the 16-B boundary below its source (the returned pointer is shifted by the source's
@@ -93,24 +66,6 @@ __device__ __forceinline__ T sum16(T v) {
     v += __shfl_xor(v, 2, 64);
     v += __shfl_xor(v, 4, 64);
     v += __shfl_xor(v, 8, 64);
-    return v;
-}
-
-template <class T>
-__device__ __forceinline__ T soc_apply_t(T v, bool is_t, T nf, T t) {
-    // SecondOrderCone.project (cones.py:113-132) for one coordinate of the block
-    if (nf <= t) return v;
-    if (nf <= -t) return T(0);
-    const T s = (nf + t) / T(2);
-    return is_t ? s : s * (v / nf);
-}
-template <class T>
-__device__ __forceinline__ T box_apply_t(T v, T lo, T hi, Ctl* ctl) {
-    // Rectangle._constrain (rectangle.py:50-59); a NaN raises ValueError on the host
-    if (lo <= v && v <= hi) return v;
-    if (v <= lo) return lo;
-    if (v >= hi) return hi;
-    atomicOr(&ctl->flags, 1);
     return v;
 }
 
@@ -214,19 +169,6 @@ __device__ __forceinline__ void tile3(const WFr<T, RT>& wf, int n, AF afun, type
 // host falls back to raocp_cp.hip otherwise).
 constexpr int kCpFamRecs = 3;
 constexpr int kCpLeafRecs = 2;
-
-// block max of non-negative values (NaN wins) -> one plain store
-__device__ __forceinline__ void blk_max_store(double v, double* dst, double* s_red) {
-    for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_xor(v, off, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double b = s_red[0];
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) b = nmax(b, s_red[i]);
-        *dst = b;
-    }
-}
 
 // ==============================================================================
 // k_cpd2 — dual. Blocks [0, nbF) families, [nbF, nbF + nbL) leaves.
@@ -366,16 +308,16 @@ __global__ void __launch_bounds__(256) k_cpd2(Dev p, Ctl* __restrict__ ctl, Bufs
                 if (live) {
                     _Pragma("unroll") for (int rt = 0; rt < RTX; ++rt) {
                         const int r = 16 * rt + lo;
-                        if (r < nx) finish(e3(p, j) + r, D3[jn * nx + r], vx[rt], soc_apply_t(vx[rt], false, nf, tt),
+                        if (r < nx) finish(e3(p, j) + r, D3[jn * nx + r], vx[rt], soc_apply(vx[rt], false, nf, tt),
                                            bx[rt][e]);
                     }
                     _Pragma("unroll") for (int rt = 0; rt < RTU; ++rt) {
                         const int r = 16 * rt + lo;
-                        if (r < nu) finish(e4(p, j) + r, D4[jn * nu + r], vu[rt], soc_apply_t(vu[rt], false, nf, tt),
+                        if (r < nu) finish(e4(p, j) + r, D4[jn * nu + r], vu[rt], soc_apply(vu[rt], false, nf, tt),
                                            bu[rt][e]);
                     }
-                    if (lo == 0) finish(p.E5 + j, d5, v5, soc_apply_t(v5, false, nf, tt), b5);
-                    if (lo == 1) finish(p.E6 + j, d6, v6, soc_apply_t(v6, true, nf, tt), b5);
+                    if (lo == 0) finish(p.E5 + j, d5, v5, soc_apply(v5, false, nf, tt), b5);
+                    if (lo == 1) finish(p.E6 + j, d6, v6, soc_apply(v6, true, nf, tt), b5);
                 }
             }
         }
@@ -416,7 +358,7 @@ __global__ void __launch_bounds__(256) k_cpd2(Dev p, Ctl* __restrict__ ctl, Bufs
                     const T dv = D7[fr.w - e7a + rr];
                     const T v = (dv + alpha * av) * ra;
                     const int bi = BI[ii];
-                    finish(fr.w + rr, dv, v, box_apply_t(v, BL[bi * (nx + nu) + rr], BH[bi * (nx + nu) + rr], ctl), bb);
+                    finish(fr.w + rr, dv, v, box_apply(v, BL[bi * (nx + nu) + rr], BH[bi * (nx + nu) + rr], ctl), bb);
                 }
             }
         }
@@ -496,24 +438,24 @@ __global__ void __launch_bounds__(256) k_cpd2(Dev p, Ctl* __restrict__ ctl, Bufs
                     _Pragma("unroll") for (int rt = 0; rt < RTX; ++rt) {
                         const int r = 16 * rt + lo;
                         if (r < nx) {
-                            finish(e11(p, l) + r, D11[qn * nx + r], vx[rt], soc_apply_t(vx[rt], false, nf, tt), bx[rt][e]);
+                            finish(e11(p, l) + r, D11[qn * nx + r], vx[rt], soc_apply(vx[rt], false, nf, tt), bx[rt][e]);
                             if (lr.z >= 0) {  // eta14 = x (box)
                                 const T zv = Xz[qn * nx + r], pv_ = Xp[qn * nx + r];
                                 const T dv = D14[lr.z - e14a + r];
                                 const T v = (dv + alpha * (T(2) * zv - pv_)) * ra;
-                                finish(lr.z + r, dv, v, box_apply_t(v, BL[lr.y * nx + r], BH[lr.y * nx + r], ctl), zv - pv_);
+                                finish(lr.z + r, dv, v, box_apply(v, BL[lr.y * nx + r], BH[lr.y * nx + r], ctl), zv - pv_);
                             }
                         }
                     }
-                    if (lo == 0) finish(p.E12 + l, d12, v12, soc_apply_t(v12, false, nf, tt), b5);
-                    if (lo == 1) finish(p.E13 + l, d13, v13, soc_apply_t(v13, true, nf, tt), b5);
+                    if (lo == 0) finish(p.E12 + l, d12, v12, soc_apply(v12, false, nf, tt), b5);
+                    if (lo == 1) finish(p.E13 + l, d13, v13, soc_apply(v13, true, nf, tt), b5);
                 }
             }
         }
     }
     double* prow = part + (size_t)bid * 6;
-    blk_max_store(m2, prow + 2, s_red[0]);
-    blk_max_store(m5, prow + 5, s_red[1]);
+    block_max_store(m2, prow + 2, s_red[0]);
+    block_max_store(m5, prow + 5, s_red[1]);
 }
 
 // ==============================================================================
@@ -881,8 +823,8 @@ __global__ void __launch_bounds__(256) k_cpp2(Dev p, Ctl* __restrict__ ctl, Bufs
         }
     }
     double* prow = part + (size_t)bid * 6;
-    blk_max_store(m0, prow + 0, s_red[0]);
-    blk_max_store(m1, prow + 1, s_red[1]);
-    blk_max_store(m3, prow + 3, s_red[2]);
-    blk_max_store(m4, prow + 4, s_red[3]);
+    block_max_store(m0, prow + 0, s_red[0]);
+    block_max_store(m1, prow + 1, s_red[1]);
+    block_max_store(m3, prow + 3, s_red[2]);
+    block_max_store(m4, prow + 4, s_red[3]);
 }

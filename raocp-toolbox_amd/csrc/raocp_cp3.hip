@@ -36,123 +36,13 @@
 // of node lo, slot t = 4 rt + e (register e of row tile rt) holding row KC h + t (t < KC;
 // zero above). In every operand and accumulator: the k index of k-step s is KC h + s, so a
 // lane's B values are consecutive entries of its node (16-B vector loads and stores where
-// KC is a multiple of 4), and the A rows are permuted (MFA<T>::rows) so that the f64
+// KC is a multiple of 4), and the A rows are permuted (MFA<T>, wrow) so that the f64
 // accumulator map (row h + 4 e) and the f32 one (4 h + e) both land row KC h + 4 rt + e in
 // slot (rt, e). A product then takes ceil(KC_out / 4) x KC_in MFMAs: no k-step is padding
 // (nx = 20: 2 x 5, against 2 x 8 with 16-row tiles).
 
-// A row lo of an output row tile lands in lane group g, register e of the accumulator
-template <class T>
-struct MFA;
-template <>
-struct MFA<double> {  // D row = h + 4 e
-    static __device__ __forceinline__ int g_of(int lo) { return lo & 3; }
-    static __device__ __forceinline__ int e_of(int lo) { return lo >> 2; }
-};
-template <>
-struct MFA<float> {  // D row = 4 h + e
-    static __device__ __forceinline__ int g_of(int lo) { return lo >> 2; }
-    static __device__ __forceinline__ int e_of(int lo) { return lo & 3; }
-};
-// the weight row A row lo of output row tile ro carries for an R-row output (-1: padding)
-template <class T, int R>
-__device__ __forceinline__ int wrow(int ro, int lo) {
-    constexpr int KC = R / 4;
-    const int t = 4 * ro + MFA<T>::e_of(lo);
-    return t < KC ? KC * MFA<T>::g_of(lo) + t : -1;
-}
-
-// weight fragments of one R x K table (column-major M[k R + r]) in the transposed form,
-// staged once per workgroup in LDS (registers are the scarce resource of this kernel: the
-// per-parent L products and three L^T accumulators stay live over the child slots):
-// lds[(ro KS + s) 64 + lane] = M[wrow(ro, lo)][K/4 h + s]
-template <class T, int R, int K>
-struct WL {
-    static_assert(R % 4 == 0 && K % 4 == 0, "row layout: R, K multiples of 4");
-    static constexpr int RO = (R / 4 + 3) / 4, KS = K / 4, N = RO * KS * 64;
-    const __attribute__((address_space(3))) T* base;
-    __device__ __forceinline__ T get(int ro, int s) const { return base[(ro * KS + s) * 64 + (threadIdx.x & 63)]; }
-    // every thread of the workgroup takes part (a __syncthreads follows)
-    template <class DP>
-    static __device__ __forceinline__ void fill(DP dst, const T* tab, int t) {
-        cglbp<T> M = (cglbp<T>)(tab + (size_t)t * R * K);
-        for (int q = threadIdx.x; q < N; q += blockDim.x) {
-            const int l = q & 63, lo = l & 15, h = l >> 4, s = (q >> 6) % KS, ro = (q >> 6) / KS;
-            const int r = wrow<T, R>(ro, lo), k = KS * h + s;
-            dst[q] = r >= 0 ? M[k * R + r] : T(0);
-        }
-    }
-};
-
-// acc[ro] += W b (b in row layout over K)
-template <class T, int R, int K>
-__device__ __forceinline__ void mmt(const WL<T, R, K>& W, const T (&b)[(K + 15) / 16][4],
-                                    typename MF<T>::v4 (&acc)[(R + 15) / 16]) {
-    _Pragma("unroll") for (int s = 0; s < WL<T, R, K>::KS; ++s)
-        _Pragma("unroll") for (int ro = 0; ro < WL<T, R, K>::RO; ++ro)
-            acc[ro] = MF<T>::mma(W.get(ro, s), b[s >> 2][s & 3], acc[ro]);
-}
-
-// 4 consecutive T at 4- / 8-B alignment (node rows start wherever the flat layout puts them)
-template <class T>
-struct V4a {
-    typedef T type __attribute__((ext_vector_type(4), aligned(sizeof(T))));
-};
-
-// slot (rt, e) of an R-row vector holds a row (t = 4 rt + e < R / 4)
-template <int R>
-__device__ __forceinline__ constexpr bool tok(int rt, int e) {
-    return 4 * rt + e < R / 4;
-}
-// row-layout load of an R-row node vector: a[rt][e] = v[R/4 h + 4 rt + e] (0 past R/4)
-template <class T, int R>
-__device__ __forceinline__ void ld_rows(cglbp<T> v, bool live, T (&a)[(R + 15) / 16][4]) {
-    typedef typename V4a<T>::type vt;
-    constexpr int KC = R / 4;
-    cglbp<T> b = v + KC * ((threadIdx.x & 63) >> 4);
-    _Pragma("unroll") for (int rt = 0; rt < (R + 15) / 16; ++rt) {
-        if (live && 4 * rt + 3 < KC) {
-            const vt w = *(const __attribute__((address_space(1))) vt*)(b + 4 * rt);
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) a[rt][e] = w[e];
-        } else {
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) a[rt][e] = (live && tok<R>(rt, e)) ? b[4 * rt + e] : T(0);
-        }
-    }
-}
-template <class T, int R>
-__device__ __forceinline__ void st_rows(glbp<T> v, bool live, const T (&a)[(R + 15) / 16][4]) {
-    typedef typename V4a<T>::type vt;
-    constexpr int KC = R / 4;
-    glbp<T> b = v + KC * ((threadIdx.x & 63) >> 4);
-    _Pragma("unroll") for (int rt = 0; rt < (R + 15) / 16; ++rt) {
-        if (!live) continue;
-        if (4 * rt + 3 < KC) {
-            vt w;
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) w[e] = a[rt][e];
-            *(__attribute__((address_space(1))) vt*)(b + 4 * rt) = w;
-        } else {
-            _Pragma("unroll") for (int e = 0; e < 4; ++e)
-                if (tok<R>(rt, e)) b[4 * rt + e] = a[rt][e];
-        }
-    }
-}
-
-// sum over the 4 lane groups (the rows of one node)
-template <class T>
-__device__ __forceinline__ T sum_h(T v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-// per-wave scratch of the kernel projection: the family's y (2C + 1 <= 9) and the
-// children's tau, s after the L^T half step (phase 5 reads them across lane groups)
-template <class T>
-struct KpScratch {
-    T y[16][9];
-    T tau[16][4];
-    T s[16][4];
-};
+// The tile layer (MFA / wrow, WL with the image's fill, mmt, V4a, tok, ld_rows_g, st_rows, sum_h,
+// KpScratch) is raocp_tile.h's; the projections are raocp_cpops.h's.
 
 // the inputs of one child slot (child block rows of d, tau of z+ and p) and of one leaf slot
 template <class T, int NX, int NU>
@@ -160,8 +50,8 @@ struct ChildIn {
     T d3[(NX + 15) / 16][4], d4[(NU + 15) / 16][4];
     T d5, d6, tz, tp;
     __device__ __forceinline__ void load(const Dev& p, cglbp<T> zp, cglbp<T> pz, cglbp<T> d, int j, bool live) {
-        ld_rows<T, NX>(d + e3(p, live ? j : 1), live, d3);
-        ld_rows<T, NU>(d + e4(p, live ? j : 1), live, d4);
+        ld_rows_g<T, NX>(d + e3(p, live ? j : 1), live, d3);
+        ld_rows_g<T, NU>(d + e4(p, live ? j : 1), live, d4);
         d5 = live ? d[p.E5 + j] : T(0);
         d6 = live ? d[p.E6 + j] : T(0);
         tz = live ? zp[p.T0 + j] : T(0);
@@ -175,11 +65,11 @@ struct LeafIn {
     int o14;
     __device__ __forceinline__ void load(const Dev& p, cglbp<T> zp, cglbp<T> pz, cglbp<T> d, int l, bool live, int bx,
                                          int m, bool box) {
-        ld_rows<T, NX>(zp + p.X0 + (size_t)(live ? l : 0) * NX, live, lz);
-        ld_rows<T, NX>(pz + p.X0 + (size_t)(live ? l : 0) * NX, live, lp);
-        ld_rows<T, NX>(d + e11(p, live ? l : m), live, d11);
+        ld_rows_g<T, NX>(zp + p.X0 + (size_t)(live ? l : 0) * NX, live, lz);
+        ld_rows_g<T, NX>(pz + p.X0 + (size_t)(live ? l : 0) * NX, live, lp);
+        ld_rows_g<T, NX>(d + e11(p, live ? l : m), live, d11);
         o14 = live && box ? o14_of<NX>(p, l, bx) : -1;
-        ld_rows<T, NX>(d + (o14 >= 0 ? o14 : 0), o14 >= 0, d14);
+        ld_rows_g<T, NX>(d + (o14 >= 0 ? o14 : 0), o14 >= 0, d14);
         d12 = live ? d[p.E12 + l] : T(0);
         d13 = live ? d[p.E13 + l] : T(0);
         sz = live ? zp[p.S0 + l] : T(0);
@@ -299,8 +189,8 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             ss += v12 * v12;
             const T nf = sqrt(ss), tt = v13;
             T ep12, x212, ep13, x213;
-            fin(d12, v12, soc_apply_t(v12, false, nf, tt), b5, ep12, x212);
-            fin(d13, v13, soc_apply_t(v13, true, nf, tt), b5, ep13, x213);
+            fin(d12, v12, soc_apply(v12, false, nf, tt), b5, ep12, x212);
+            fin(d13, v13, soc_apply(v13, true, nf, tt), b5, ep13, x213);
             if (pside && live && h == 0) {
                 ks.s[lo][k] = sz - alpha * (T(0.5) * (ep12 + ep13));
                 account(sp, sz, T(0.5) * ((d12 - ep12) + (d13 - ep13)), T(0.5) * (x212 + x213));
@@ -312,7 +202,7 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 T ep = T(0), x2 = T(0);
                 if (live && tok<NX>(rt, e))
-                    fin(d11[rt][e], v11[rt][e], soc_apply_t(v11[rt][e], false, nf, tt), lb[rt][e], ep, x2);
+                    fin(d11[rt][e], v11[rt][e], soc_apply(v11[rt][e], false, nf, tt), lb[rt][e], ep, x2);
                 eA[rt][e] = ep;
                 eW[rt][e] = d11[rt][e] - ep;
                 eC[rt][e] = x2;
@@ -327,13 +217,13 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             if (o14 >= 0) {
                 const int bl = p.iBl[l];
                 T l14[RX][4], h14[RX][4], e14[RX][4];
-                ld_rows<T, NX>((cglbp<T>)p.blo_l + (size_t)bl * NX, true, l14);
-                ld_rows<T, NX>((cglbp<T>)p.bhi_l + (size_t)bl * NX, true, h14);
+                ld_rows_g<T, NX>((cglbp<T>)p.blo_l + (size_t)bl * NX, true, l14);
+                ld_rows_g<T, NX>((cglbp<T>)p.bhi_l + (size_t)bl * NX, true, h14);
                 _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                     T ep = T(0), x2 = T(0);
                     if (tok<NX>(rt, e)) {
                         const T v = (d14[rt][e] + alpha * (T(2) * lz[rt][e] - lp[rt][e])) * ra;
-                        fin(d14[rt][e], v, box_apply_t(v, l14[rt][e], h14[rt][e], ctl), lz[rt][e] - lp[rt][e], ep, x2);
+                        fin(d14[rt][e], v, box_apply(v, l14[rt][e], h14[rt][e], ctl), lz[rt][e] - lp[rt][e], ep, x2);
                     }
                     e14[rt][e] = ep;
                     gA[rt][e] += ep;
@@ -437,10 +327,10 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
         {
             // the parent's x, u rows (reloaded in phase 3: registers, not HBM, are short here)
             T xz[RX][4], xp[RX][4], uz[RU][4], up[RU][4];
-            ld_rows<T, NX>(zp + p.X0 + (size_t)i * NX, live, xz);
-            ld_rows<T, NX>(pz + p.X0 + (size_t)i * NX, live, xp);
-            ld_rows<T, NU>(zp + p.U0 + (size_t)i * NU, live, uz);
-            ld_rows<T, NU>(pz + p.U0 + (size_t)i * NU, live, up);
+            ld_rows_g<T, NX>(zp + p.X0 + (size_t)i * NX, live, xz);
+            ld_rows_g<T, NX>(pz + p.X0 + (size_t)i * NX, live, xp);
+            ld_rows_g<T, NU>(zp + p.U0 + (size_t)i * NU, live, uz);
+            ld_rows_g<T, NU>(pz + p.U0 + (size_t)i * NU, live, up);
             T a1[RX][4], a2[RX][4];
             _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 a1[rt][e] = T(2) * xz[rt][e] - xp[rt][e];
@@ -495,7 +385,7 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 T ep = T(0), x2 = T(0);
                 if (live && tok<NX>(rt, e))
-                    fin(d3[rt][e], v3[rt][e], soc_apply_t(v3[rt][e], false, nf, tt), qb[rt][e], ep, x2);
+                    fin(d3[rt][e], v3[rt][e], soc_apply(v3[rt][e], false, nf, tt), qb[rt][e], ep, x2);
                 e3A[rt][e] = ep;
                 e3W[rt][e] = d3[rt][e] - ep;
                 e3C[rt][e] = x2;
@@ -510,7 +400,7 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             _Pragma("unroll") for (int rt = 0; rt < RU; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 T ep = T(0), x2 = T(0);
                 if (live && tok<NU>(rt, e))
-                    fin(d4[rt][e], v4_[rt][e], soc_apply_t(v4_[rt][e], false, nf, tt), ub[rt][e], ep, x2);
+                    fin(d4[rt][e], v4_[rt][e], soc_apply(v4_[rt][e], false, nf, tt), ub[rt][e], ep, x2);
                 e4A[rt][e] = ep;
                 e4W[rt][e] = d4[rt][e] - ep;
                 e4C[rt][e] = x2;
@@ -523,8 +413,8 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             }
             // eta5 / eta6 and tau_j of the half step (before the kernel projection)
             T ep5, x25, ep6, x26;
-            fin(d5, v5, soc_apply_t(v5, false, nf, tt), b5, ep5, x25);
-            fin(d6, v6, soc_apply_t(v6, true, nf, tt), b5, ep6, x26);
+            fin(d5, v5, soc_apply(v5, false, nf, tt), b5, ep5, x25);
+            fin(d6, v6, soc_apply(v6, true, nf, tt), b5, ep6, x26);
             if (live && h == 0) eo[p.E5 + j] = ep5;
             if (live && h == 1) eo[p.E6 + j] = ep6;
             if (live && h == 0) {
@@ -566,25 +456,25 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
         // L^T = Gamma' eta7 + sqrtQ (sum of the children's eta3) (operators.py:73-85)
         {
             T xz[RX][4], xp[RX][4], uz[RU][4], up[RU][4];
-            ld_rows<T, NX>(zp + p.X0 + (size_t)i * NX, live, xz);
-            ld_rows<T, NX>(pz + p.X0 + (size_t)i * NX, live, xp);
-            ld_rows<T, NU>(zp + p.U0 + (size_t)i * NU, live, uz);
-            ld_rows<T, NU>(pz + p.U0 + (size_t)i * NU, live, up);
+            ld_rows_g<T, NX>(zp + p.X0 + (size_t)i * NX, live, xz);
+            ld_rows_g<T, NX>(pz + p.X0 + (size_t)i * NX, live, xp);
+            ld_rows_g<T, NU>(zp + p.U0 + (size_t)i * NU, live, uz);
+            ld_rows_g<T, NU>(pz + p.U0 + (size_t)i * NU, live, up);
             T d7x[RX][4], d7u[RU][4];
-            ld_rows<T, NX>(d + (o7 >= 0 ? o7 : 0), o7 >= 0, d7x);
-            ld_rows<T, NU>(d + (o7 >= 0 ? o7 + NX : 0), o7 >= 0, d7u);
+            ld_rows_g<T, NX>(d + (o7 >= 0 ? o7 : 0), o7 >= 0, d7x);
+            ld_rows_g<T, NU>(d + (o7 >= 0 ? o7 + NX : 0), o7 >= 0, d7u);
             const int bi = o7 >= 0 ? p.iBnl[i] : 0;
             cglbp<T> blo = (cglbp<T>)p.blo_nl + (size_t)bi * (NX + NU), bhi = (cglbp<T>)p.bhi_nl + (size_t)bi * (NX + NU);
             v4 gxA[RX], gxW[RX], gxC[RX], guA[RU], guW[RU], guC[RU];
             {
                 T lx[RX][4], hx[RX][4], e7[RX][4];
-                ld_rows<T, NX>(blo, o7 >= 0, lx);
-                ld_rows<T, NX>(bhi, o7 >= 0, hx);
+                ld_rows_g<T, NX>(blo, o7 >= 0, lx);
+                ld_rows_g<T, NX>(bhi, o7 >= 0, hx);
                 _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                     T ep = T(0), x2 = T(0);
                     if (o7 >= 0 && tok<NX>(rt, e)) {
                         const T v = (d7x[rt][e] + alpha * (T(2) * xz[rt][e] - xp[rt][e])) * ra;
-                        fin(d7x[rt][e], v, box_apply_t(v, lx[rt][e], hx[rt][e], ctl), xz[rt][e] - xp[rt][e], ep, x2);
+                        fin(d7x[rt][e], v, box_apply(v, lx[rt][e], hx[rt][e], ctl), xz[rt][e] - xp[rt][e], ep, x2);
                     }
                     e7[rt][e] = ep;
                     gxA[rt][e] = ep;
@@ -595,13 +485,13 @@ __global__ void __launch_bounds__(256) k_cp3(Dev p, Ctl* __restrict__ ctl, Bufs 
             }
             {
                 T lu[RU][4], hu[RU][4], e7u[RU][4];
-                ld_rows<T, NU>(blo + NX, o7 >= 0, lu);
-                ld_rows<T, NU>(bhi + NX, o7 >= 0, hu);
+                ld_rows_g<T, NU>(blo + NX, o7 >= 0, lu);
+                ld_rows_g<T, NU>(bhi + NX, o7 >= 0, hu);
                 _Pragma("unroll") for (int rt = 0; rt < RU; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                     T ep = T(0), x2 = T(0);
                     if (o7 >= 0 && tok<NU>(rt, e)) {
                         const T v = (d7u[rt][e] + alpha * (T(2) * uz[rt][e] - up[rt][e])) * ra;
-                        fin(d7u[rt][e], v, box_apply_t(v, lu[rt][e], hu[rt][e], ctl), uz[rt][e] - up[rt][e], ep, x2);
+                        fin(d7u[rt][e], v, box_apply(v, lu[rt][e], hu[rt][e], ctl), uz[rt][e] - up[rt][e], ep, x2);
                     }
                     e7u[rt][e] = ep;
                     guA[rt][e] = ep;

@@ -22,13 +22,13 @@
 // per workgroup; other trees read their node's table from global memory at its use.
 
 #include "raocp_cp4.h"
-#include "raocp_tile.h"
+#include "raocp_cpops.h"
 
 namespace raocp {
 namespace {
 
-// (glbp / cglbp, MF, WL, mmt, ld_rows, ldz, st_rows, ld_rows_lds, sum_h, the cone and box
-// projections, KpScratch, dma_wait: raocp_tile.h)
+// (glbp / cglbp, MF, WL, mmt, ld_rows, ldz, st_rows, ld_rows_lds, sum_h, KpScratch, dma_wait:
+// raocp_tile.h; the cone and box projections: raocp_cpops.h)
 
 // ---- the operands of one leaf (a leaf tile's lane, or a leaf slot of a leaf-parent family)
 template <class T, int NX, int BXL>
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
             const int ch = c0 + lane;
             if (ch < chunks)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) double*)(img + 2 * ch),
-                                                 (lds_d*)wlds_ + 2 * c0, 16, 0, 0);
+                                                 (ldsd*)wlds_ + 2 * c0, 16, 0, 0);
         }
         const bool onen = BXN == 1 && p.nBnl <= 1, onel = BXL == 1 && p.nBl <= 1;
         for (int e = threadIdx.x; e < 2 * (NX + NU) + 2 * NX; e += blockDim.x) {
@@ -249,8 +249,8 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
         ss += v12 * v12;
         const T nf = sqrt(ss), tt = v13;
         T ep12, x212, ep13, x213;
-        fin(d12, v12, soc_apply_t(v12, false, nf, tt), b5, ep12, x212);
-        fin(d13, v13, soc_apply_t(v13, true, nf, tt), b5, ep13, x213);
+        fin(d12, v12, soc_apply(v12, false, nf, tt), b5, ep12, x212);
+        fin(d13, v13, soc_apply(v13, true, nf, tt), b5, ep13, x213);
         if (pside && live && h == 0) {
             ks.s[lo][k] = sz - alpha * (T(0.5) * (ep12 + ep13));
             account(sp, sz, T(0.5) * ((d12 - ep12) + (d13 - ep13)), T(0.5) * (x212 + x213));
@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
         _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
             T ep = T(0), x2 = T(0);
             if (live && tok<NX>(rt, e))
-                fin(d11[rt][e], v11[rt][e], soc_apply_t(v11[rt][e], false, nf, tt), lb[rt][e], ep, x2);
+                fin(d11[rt][e], v11[rt][e], soc_apply(v11[rt][e], false, nf, tt), lb[rt][e], ep, x2);
             eA[rt][e] = ep;
             eW[rt][e] = d11[rt][e] - ep;
             eC[rt][e] = x2;
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
                 T ep = T(0), x2 = T(0);
                 if (tok<NX>(rt, e)) {
                     const T v = (d14[rt][e] + alpha * (T(2) * lz[rt][e] - lp[rt][e])) * ra;
-                    fin(d14[rt][e], v, box_apply_t(v, l14[rt][e], h14[rt][e], ctl), lz[rt][e] - lp[rt][e], ep, x2);
+                    fin(d14[rt][e], v, box_apply(v, l14[rt][e], h14[rt][e], ctl), lz[rt][e] - lp[rt][e], ep, x2);
                 }
                 e14[rt][e] = ep;
                 gA[rt][e] += ep;
@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
             _Pragma("unroll") for (int rt = 0; rt < RX; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 T ep = T(0), x2 = T(0);
                 if (live && tok<NX>(rt, e))
-                    fin(d3[rt][e], v3[rt][e], soc_apply_t(v3[rt][e], false, nf, tt), qb[rt][e], ep, x2);
+                    fin(d3[rt][e], v3[rt][e], soc_apply(v3[rt][e], false, nf, tt), qb[rt][e], ep, x2);
                 e3A[rt][e] = ep;
                 e3W[rt][e] = d3[rt][e] - ep;
                 e3C[rt][e] = x2;
@@ -440,7 +440,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
             _Pragma("unroll") for (int rt = 0; rt < RU; ++rt) _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                 T ep = T(0), x2 = T(0);
                 if (live && tok<NU>(rt, e))
-                    fin(d4[rt][e], v4_[rt][e], soc_apply_t(v4_[rt][e], false, nf, tt), ub[rt][e], ep, x2);
+                    fin(d4[rt][e], v4_[rt][e], soc_apply(v4_[rt][e], false, nf, tt), ub[rt][e], ep, x2);
                 e4A[rt][e] = ep;
                 e4W[rt][e] = d4[rt][e] - ep;
                 e4C[rt][e] = x2;
@@ -452,8 +452,8 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
                 suC[rt][e] += e4C[rt][e];
             }
             T ep5, x25, ep6, x26;
-            fin(d5, v5, soc_apply_t(v5, false, nf, tt), b5, ep5, x25);
-            fin(d6, v6, soc_apply_t(v6, true, nf, tt), b5, ep6, x26);
+            fin(d5, v5, soc_apply(v5, false, nf, tt), b5, ep5, x25);
+            fin(d6, v6, soc_apply(v6, true, nf, tt), b5, ep6, x26);
             if (live && h == 0) eo[p.E5 + j] = ep5;
             if (live && h == 1) eo[p.E6 + j] = ep6;
             if (live && h == 0) {
@@ -514,7 +514,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
                     T ep = T(0), x2 = T(0);
                     if (live && tok<NX>(rt, e)) {
                         const T v = (d7x[rt][e] + alpha * (T(2) * xz[rt][e] - xp[rt][e])) * ra;
-                        fin(d7x[rt][e], v, box_apply_t(v, lx[rt][e], hx[rt][e], ctl), xz[rt][e] - xp[rt][e], ep, x2);
+                        fin(d7x[rt][e], v, box_apply(v, lx[rt][e], hx[rt][e], ctl), xz[rt][e] - xp[rt][e], ep, x2);
                     }
                     e7[rt][e] = ep;
                     gxA[rt][e] = ep;
@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(256) k_cp4(Dev p, Ctl* __restrict__ ctl, Bufs 
                     T ep = T(0), x2 = T(0);
                     if (live && tok<NU>(rt, e)) {
                         const T v = (d7u[rt][e] + alpha * (T(2) * uz[rt][e] - up[rt][e])) * ra;
-                        fin(d7u[rt][e], v, box_apply_t(v, lu[rt][e], hu[rt][e], ctl), uz[rt][e] - up[rt][e], ep, x2);
+                        fin(d7u[rt][e], v, box_apply(v, lu[rt][e], hu[rt][e], ctl), uz[rt][e] - up[rt][e], ep, x2);
                     }
                     e7u[rt][e] = ep;
                     guA[rt][e] = ep;

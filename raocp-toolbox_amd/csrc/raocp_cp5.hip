@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256, LPF ? 1 : 2) k_cp5_leaf(Dev p, Ctl* ctl, 
     LeafOps<T, NX, BXL> cur;
     if (LPF) cur.load(p, zp, pz, d, l0 + 16 * gw + lo, gw < nL && l0 + 16 * gw + lo < l1);
     {
-        lds_fill((lds_d*)wlds_, img, WP::N * (int)sizeof(T) / 16);  // the sqrtPf fragments
+        lds_fill((ldsd*)wlds_, img, WP::N * (int)sizeof(T) / 16);  // the sqrtPf fragments
         for (int e = threadIdx.x; e < 2 * NX; e += blockDim.x)  // one box table (cp5_supported)
             bl_[e] = BXL == 1 ? (e < NX ? ((cglbp<T>)p.blo_l)[e] : ((cglbp<T>)p.bhi_l)[e - NX]) : T(0);
     }
@@ -311,7 +311,7 @@ __global__ void __launch_bounds__(64 * C, 2) k_cp5_fams(Dev p, Ctl* ctl, Bufs bf
     cglbp<T> cond = (cglbp<T>)p.cond;
     lT* bl_ = (lT*)blds_;
     {
-        lds_fill((lds_d*)wlds_, img, (WQ::N + WR::N) * (int)sizeof(T) / 16);  // [sqrtQ | sqrtR]
+        lds_fill((ldsd*)wlds_, img, (WQ::N + WR::N) * (int)sizeof(T) / 16);  // [sqrtQ | sqrtR]
         for (int e = threadIdx.x; e < 2 * (NX + NU); e += blockDim.x)  // one box table (cp5_supported)
             bl_[e] = BXN == 1 ? (e < NX + NU ? ((cglbp<T>)p.blo_nl)[e] : ((cglbp<T>)p.bhi_nl)[e - (NX + NU)]) : T(0);
     }
@@ -649,7 +649,7 @@ __global__ void __launch_bounds__(128 * C) k_cp6(Dev p, Ctl* ctl, Bufs bf, doubl
     };
     stamp();
     {
-        lds_fill((lds_d*)wlds_, img, (2 * WQ::N + WR::N) * (int)sizeof(T) / 16);  // [sqrtQ | sqrtR | sqrtPf]
+        lds_fill((ldsd*)wlds_, img, (2 * WQ::N + WR::N) * (int)sizeof(T) / 16);  // [sqrtQ | sqrtR | sqrtPf]
         for (int e = threadIdx.x; e < 2 * (NX + NU) + 2 * NX; e += blockDim.x) {  // one box table each
             T v = T(0);
             if (e < NX + NU) v = BXN == 1 ? ((cglbp<T>)p.blo_nl)[e] : T(0);

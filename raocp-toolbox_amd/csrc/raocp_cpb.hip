@@ -35,6 +35,7 @@
 // sqrt Pf, the box bounds) are staged in LDS once per launch when they fit kCpbLdsTabs.
 
 #include "raocp_cpb.h"
+#include "raocp_cpops.h"
 
 namespace raocp {
 namespace {
@@ -48,12 +49,6 @@ template <class T>
 using cl = const __attribute__((address_space(3))) T*;
 typedef __attribute__((address_space(1))) const int glbi;
 
-// max for the residual reductions in T: a NaN operand wins (raocp_common.h nmax)
-template <class T>
-__device__ __forceinline__ T nmx(T a, T b) {
-    return (a > b || a != a) ? a : b;
-}
-
 constexpr __host__ __device__ int rup_(int a, int b) { return (a + b - 1) / b * b; }
 // the row strides of the dynamics tables (raocp_dyn.hip tstride)
 constexpr __host__ __device__ int tstride_(int k) { return (k / 2) % 2 == 0 ? k + 2 : k; }
@@ -62,23 +57,7 @@ __device__ __forceinline__ int e3(const Dev& p, int j) { return p.E3 + 1 + (j - 
 __device__ __forceinline__ int e4(const Dev& p, int j) { return p.E4 + 1 + (j - 1) * p.nu; }
 __device__ __forceinline__ int e11(const Dev& p, int l) { return p.E11 + p.m + (l - p.m) * p.nx; }
 
-// SecondOrderCone.project (cones.py:113-132) for one coordinate of the block
-template <class T>
-__device__ __forceinline__ T soc_apply(T v, bool is_t, T nf, T t) {
-    if (nf <= t) return v;
-    if (nf <= -t) return T(0);
-    const T s = (nf + t) / T(2);
-    return is_t ? s : s * (v / nf);
-}
-// Rectangle._constrain (rectangle.py:50-59); a NaN stays and raises the lane's flag
-template <class T>
-__device__ __forceinline__ T box_apply(T v, T lo, T hi, bool& nan) {
-    if (lo <= v && v <= hi) return v;
-    if (v <= lo) return lo;
-    if (v >= hi) return hi;
-    nan = true;
-    return v;
-}
+// (soc_apply, box_apply with the lane's NaN flag, nmx: raocp_cpops.h)
 
 // the tables every instance shares, in LDS (PT = cl<T>) or in HBM (PT = cg<T>)
 template <class PT>

@@ -1,8 +1,9 @@
-// raocp_cpops.h — entry arithmetic and reductions of the fused CP tiles shared by the
-// translation units raocp_cp5.hip (k_cp5, k_cp6) and raocp_dynr.hip (k_drc): the residual maxima
-// with numpy's NaN propagation, the second-order-cone and box projections as selects, the
-// per-workgroup residual row and the LDS forms of a row-layout vector. Header-only, anonymous
-// namespace (each translation unit gets its own copies).
+// raocp_cpops.h — entry arithmetic and reductions of the CP kernels, defined once for every
+// translation unit: the residual maxima with numpy's NaN propagation, the per-entry residual
+// terms of the fused tiles (Resid), the second-order-cone and box projections in branch form
+// (soc_apply, box_apply) and as selects (Soc, box_sel: k_cp5 / k_cp6 / k_drc), the
+// per-workgroup residual reductions and the LDS forms of a row-layout vector. Header-only,
+// anonymous namespace (each translation unit gets its own copies).
 #pragma once
 
 #include "raocp_tile.h"
@@ -48,7 +49,17 @@ struct Amax<double> {
 };
 #endif
 
-// the six residual maxima of a wave, and the per-entry terms (raocp_cp3.hip fin / account).
+// max in T for k_cpb's residual reductions: a NaN operand wins (raocp_common.h nmax)
+template <class T>
+__device__ __forceinline__ T nmx(T a, T b) {
+    return (a > b || a != a) ? a : b;
+}
+
+// the six residual maxima of a wave, and the per-entry terms (raocp_cp3.hip fin / account) in
+// the * ra arithmetic (ra = 1 / alpha), for k_cp5 / k_cp6 / k_drc. The lambdas of the same
+// terms in k_cpd2 / k_cpp2 / k_cp3 / k_cp4 (double maxima through nmax) and, dividing by alpha
+// (an ulp apart), in k_cp_dual / k_cp_primal / k_cpd / k_cpp and k_cpb's Maxima stay where they
+// are: replacing them by this struct's methods changed those kernels' code objects.
 // A lane past its tile's nodes has zero operands (ldz / ld_rows) and zero box bounds, so
 // every one of its terms is zero: nothing to mask.
 template <class T>
@@ -86,6 +97,33 @@ struct Resid {
         m4.add(dl1);
     }
 };
+// SecondOrderCone.project (cones.py:113-132) for one coordinate of the block, in branch form
+// (every CP kernel but k_cp5 / k_cp6 / k_drc, whose select form Soc follows)
+template <class T>
+__device__ __forceinline__ T soc_apply(T v, bool is_t, T nf, T t) {
+    if (nf <= t) return v;
+    if (nf <= -t) return T(0);
+    const T s = (nf + t) / T(2);
+    return is_t ? s : s * (v / nf);
+}
+// Rectangle._constrain (rectangle.py:50-59) in branch form; a NaN stays (the host raises
+// ValueError) and is reported on ctl->flags, or on the lane's flag (k_cpb)
+template <class T>
+__device__ __forceinline__ T box_apply(T v, T lo, T hi, Ctl* ctl) {
+    if (lo <= v && v <= hi) return v;
+    if (v <= lo) return lo;
+    if (v >= hi) return hi;
+    atomicOr(&ctl->flags, 1);
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T box_apply(T v, T lo, T hi, bool& nan) {
+    if (lo <= v && v <= hi) return v;
+    if (v <= lo) return lo;
+    if (v >= hi) return hi;
+    nan = true;
+    return v;
+}
 
 // SecondOrderCone.project (cones.py:113-132) of one block as per-entry selects: the block is
 // kept (|first| <= t), zeroed (|first| <= -t) or scaled, first * (nf + t) / (2 nf) and
@@ -112,6 +150,21 @@ __device__ __forceinline__ T box_sel(T v, T lo, T hi, bool& nan) {
 }
 __device__ __forceinline__ void flag_nan(Ctl* ctl, bool nan, int bit = 1) {
     if (__builtin_amdgcn_ballot_w64(nan) != 0 && (threadIdx.x & 63) == 0) atomicOr(&ctl->flags, bit);
+}
+
+// block-wide max of non-negative doubles (NaN wins) -> one plain store per block (the per-block
+// partials are reduced by k_cp_check; no atomics on a single hot address); s_red: one double
+// per wave. The node-block kernels (k_cp_dual / k_cp_primal, k_cpd / k_cpp, k_cpd2 / k_cpp2).
+__device__ __forceinline__ void block_max_store(double v, double* dst, double* s_red) {
+    for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double b = s_red[0];
+        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) b = nmax(b, s_red[i]);
+        *dst = b;
+    }
 }
 
 // per-block residual maxima -> one row of `part` (plain stores, k_cp_check reduces). A wave's

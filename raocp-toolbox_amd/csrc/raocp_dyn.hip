@@ -544,7 +544,7 @@ __device__ __forceinline__ void dma_rows(ldsd* dst, int w, const double* src, in
         return c < cc ? src + (size_t)r * sstride + 2 * c : zp;
     });
 }
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// (dma_wait: raocp_tile.h)
 // The CP stop flag, read by a kernel AFTER it has issued its prologue loads: the flag was
 // written by the previous launch (another XCD's L2), so the load costs a memory round trip,
 // and a scalar load is waited for where its value is first needed — at the top of the

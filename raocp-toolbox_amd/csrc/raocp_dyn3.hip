@@ -2,7 +2,8 @@
 // MFMA wave tasks, for trees with one branching factor C <= 4 whose child slot k has the
 // same (A, B) pair at every parent of a stage and whose parents of a stage share one
 // offline class (host checks, raocp_capi.hip): the i.i.d. trees of configs 2, 4 and 5.
-// Included by raocp_kernels.hip after raocp_cp3.hip (the row layout, WL fragments, MFA).
+// Included by raocp_kernels.hip; the row layout, wrow / MFA and ld_rows_g / st_rows are
+// raocp_tile.h's.
 //
 // Device form (raocp_dyn.hip header):
 //   backward, stage t = N-1 .. 0, a tile of 16 parents i (lane lo = parent):
@@ -162,11 +163,11 @@ __global__ void __launch_bounds__(512) k_dy3_back(Dev p, const Ctl* ctl, ChkArg 
         _Pragma("unroll") for (int k = 0; k < 4; ++k) {
             if (k < k0 || k >= k1) continue;
             const int j = 1 + C * (live ? i : st.i0) + k;
-            if (st.leaf) ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)j * NX, live, qj[k]);
-            else ld_rows<T, NX>((cglbp<T>)qb + (size_t)j * NX, live, qj[k]);
+            if (st.leaf) ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)j * NX, live, qj[k]);
+            else ld_rows_g<T, NX>((cglbp<T>)qb + (size_t)j * NX, live, qj[k]);
         }
-        ld_rows<T, NU>((cglbp<T>)z + p.U0 + (size_t)i * NU, live, u);
-        ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
+        ld_rows_g<T, NU>((cglbp<T>)z + p.U0 + (size_t)i * NU, live, u);
+        ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
     };
     // fp32 (config 5: two tiles per wave in the widest stage): a wave per tile, its next tile's
     // rows double-buffered, issued before the current tile's slot products, so that a wide
@@ -181,10 +182,10 @@ __global__ void __launch_bounds__(512) k_dy3_back(Dev p, const Ctl* ctl, ChkArg 
             cglbp<T> src = st.leaf ? (cglbp<T>)z + p.X0 : (cglbp<T>)qb;
             _Pragma("unroll") for (int k = 0; k < 4; ++k) {
                 const int kk = k < C ? k : C - 1;
-                ld_rows<T, NX>(src + (size_t)(1 + C * ic + kk) * NX, true, q[k]);
+                ld_rows_g<T, NX>(src + (size_t)(1 + C * ic + kk) * NX, true, q[k]);
             }
-            ld_rows<T, NU>((cglbp<T>)z + p.U0 + (size_t)ic * NU, true, uu);
-            ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)ic * NX, true, xx);
+            ld_rows_g<T, NU>((cglbp<T>)z + p.U0 + (size_t)ic * NU, true, uu);
+            ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)ic * NX, true, xx);
         };
         ld_all(min(gw, ntile - 1), qj, u, x);
         dma_wait();
@@ -317,9 +318,9 @@ __global__ void __launch_bounds__(512) k_dy3_fwd(Dev p, const Ctl* ctl, double* 
         const int task = sp ? tk / C : tk;
         const int i = st.i0 + 16 * task + lo;
         const bool live = i < st.i1;
-        if (i == 0) ld_rows<T, NX>((cglbp<T>)x0_, true, x);  // x_0 = x0bar (cache.py:283)
-        else ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
-        ld_rows<T, NU>(db + (size_t)i * NU, live, d);
+        if (i == 0) ld_rows_g<T, NX>((cglbp<T>)x0_, true, x);  // x_0 = x0bar (cache.py:283)
+        else ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
+        ld_rows_g<T, NU>(db + (size_t)i * NU, live, d);
     };
     if (gw < ntask) load(gw);
     dma_wait();
@@ -400,11 +401,11 @@ __global__ void __launch_bounds__(512) k_dy3_top_back(Dev p, const Ctl* ctl, dou
         const bool live = act && i < st.i1;
         if (!act) return;
         const int j = 1 + C * (live ? i : st.i0) + k;
-        if (st.leaf) ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)j * NX, live, qj);
-        else ld_rows<T, NX>((cglbp<T>)qb + (size_t)j * NX, live, qj);
+        if (st.leaf) ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)j * NX, live, qj);
+        else ld_rows_g<T, NX>((cglbp<T>)qb + (size_t)j * NX, live, qj);
         if (k == 0) {
-            ld_rows<T, NU>((cglbp<T>)z + p.U0 + (size_t)i * NU, live, u);
-            ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
+            ld_rows_g<T, NU>((cglbp<T>)z + p.U0 + (size_t)i * NU, live, u);
+            ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
         }
     };
     // the child slots' tables [B_k' | A_k'] depend on the slot's (A, B) kind only: when every
@@ -502,9 +503,9 @@ __global__ void __launch_bounds__(512) k_dy3_top_fwd(Dev p, const Ctl* ctl, doub
         const int task = tk / C;
         const int i = st.i0 + 16 * task + lo;
         const bool live = i < st.i1;
-        if (i == 0) ld_rows<T, NX>((cglbp<T>)x0_, true, x);  // x_0 = x0bar (cache.py:283)
-        else ld_rows<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
-        ld_rows<T, NU>(db + (size_t)i * NU, live, d);
+        if (i == 0) ld_rows_g<T, NX>((cglbp<T>)x0_, true, x);  // x_0 = x0bar (cache.py:283)
+        else ld_rows_g<T, NX>((cglbp<T>)z + p.X0 + (size_t)i * NX, live, x);
+        ld_rows_g<T, NU>(db + (size_t)i * NU, live, d);
     };
     for (int si = 0; si < tp.ts; ++si) {
         const Dy3Stage st = tp.st[si];

@@ -13,6 +13,11 @@
 // Reference formulas are cited as /root/reference file:line.
 
 #include "raocp_common.h"
+// the tile layer, the projections and the block reductions every CP kernel shares
+// (raocp_tile.h through raocp_cpops.h); sum_h by shuffles in this unit, as k_cp3 was written
+// (the row-swap form is k_cp4's and k_cp5 / k_cp6's)
+#define RAOCP_SUMH_SHFL
+#include "raocp_cpops.h"
 
 namespace raocp {
 
@@ -147,21 +152,6 @@ __device__ __forceinline__ void dot_lt3(PM m, int ms, PV dA, PV dP, PV cc, int n
         sA = a0 + a1;
         sW = w0 + w1;
         sC = c0 + c1;
-    }
-}
-
-// block-wide max of non-negative doubles -> one plain store per block (the per-block
-// partials are reduced by k_cp_check; no atomics on a single hot address)
-__device__ void block_max_store(double v, double* dst, double* s_red) {
-    for (int off = 32; off > 0; off >>= 1) v = nmax(v, __shfl_xor(v, off, 64));
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[w] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double b = s_red[0];
-        for (int i = 1; i < (int)(blockDim.x >> 6); ++i) b = nmax(b, s_red[i]);
-        *dst = b;
     }
 }
 
@@ -449,22 +439,7 @@ __global__ void __launch_bounds__(kBlock) k_cp_primal(Dev p, Ctl* __restrict__ c
 // WITH_L = false is the standalone prox_gconj (Cache.proximal_of_g_conjugate) on `d`
 // in place (eta_half = d).
 // ==============================================================================
-__device__ __forceinline__ double soc_apply(double v, bool is_t, double nf, double t) {
-    // SecondOrderCone.project (cones.py:113-132) for one coordinate of the block
-    if (nf <= t) return v;
-    if (nf <= -t) return 0.0;
-    const double s = (nf + t) / 2.0;
-    return is_t ? s : s * (v / nf);
-}
-
-__device__ __forceinline__ double box_apply(double v, double lo, double hi, Ctl* ctl) {
-    // Rectangle._constrain (rectangle.py:50-59)
-    if (lo <= v && v <= hi) return v;
-    if (v <= lo) return lo;
-    if (v >= hi) return hi;
-    atomicOr(&ctl->flags, 1);
-    return v;
-}
+// (soc_apply, box_apply: raocp_cpops.h, here at double)
 
 // mode (standalone only): bit0 PROX (scale, halves, Moreau output) else projection output Pi(d);
 // bit1 process the nonleaf part (eta1..eta7, SOC per child); bit2 the leaf part (eta11..eta14).
