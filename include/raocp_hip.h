@@ -148,6 +148,11 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * runs its forward levels from a zero root x row while it waits for that row and adds the
  * composed map's product with the row once it has landed; "" when none is (RAOCP_DR_XFER=0,
  * RAOCP_DR_FWD=0, a one-tier plan or one with a tier of more than 4 levels, another sweep);
+ * op 17: the kernels of raocp_evaluate, "k_eval_nodes<double> + k_eval_sweep<double> xS" with S
+ * the number of sweep launches ("<float>" on an fp32 context); op 18: the kernel of
+ * raocp_cp_batch_evaluate, "k_eval_batch<double>" / "k_eval_batch<float>", or "" when the batch
+ * evaluation runs the kernels of op 17 over each stored primal (after a batch: by how that batch
+ * ran; before any: by how one would run now, as op 13 reports it);
  * written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
@@ -249,6 +254,42 @@ int raocp_cp_batch_mpc(raocp_ctx* ctx, int B, int T, const double* x0 /*[B][nx]*
                        double* X /*[B][T+1][nx]*/, double* U /*[B][T][nu]*/, double* cost /*[B][T]*/,
                        int* status /*[B][T]*/, int* iters /*[B][T]*/, double* err /*[B][T][3]*/);
 
+/* Evaluate a primal: the risk-averse cost of its policy and how far it is from feasible
+ * (raocp_eval.hip). With l_j = |sqrtQ_j x_anc(j)|^2 + |sqrtR_j u_anc(j)|^2 the stage cost of
+ * node j >= 1 and V_l = |sqrtPf_l x_l|^2 the terminal cost of leaf l, the cost-to-go of a
+ * nonleaf node is V_i = AVaR_{alpha_i, cond}((l_j + V_j) over the children j of i), the maximum
+ * of mu'Z over {alpha mu <= p, mu >= 0, 1'mu = 1} (risks.py:28-35; alpha = 0 the plain maximum,
+ * alpha = 1 the expectation). out[]:
+ *   RAOCP_EVAL_COST  V_0
+ *   RAOCP_EVAL_S0    the primal's own epigraph variable s_0 (equals V_0 only at convergence)
+ *   RAOCP_EVAL_BOX   the largest max(lo - w, w - hi, 0) over every active box (nonleaf rows
+ *                    w = [x_i; u_i], leaf rows w = x_l); 0 without boxes, infinite bounds never
+ *                    violate
+ *   RAOCP_EVAL_DYN   max(|x_0 - x0|_inf, max_j |x_j - A_j x_anc(j) - B_j u_anc(j)|_inf), x0 the
+ *                    initial state of raocp_set_initial_state / the last raocp_cp_run
+ * A NaN in the primal surfaces: the maxima keep it and the cost becomes NaN. Values are loaded
+ * in the context's scalar type; all arithmetic is double on a context of either precision.
+ * z NULL: the context's current primal; else a flat primal (host, or device with
+ * RAOCP_DEVICE_PTR in `flags`: double* on an fp64 context, float* on an fp32 one).
+ * node_values NULL or a host array [n]: V_i of every node (leaves: the terminal cost).
+ * Nothing of the context changes (iterate, initial state, batch slabs, captured graphs).
+ * Errors: RAOCP_ERR_ARG for a NULL out; RAOCP_ERR_STATE without an initial state or on a
+ * sharded context. kernel_info op 17 names the kernels. */
+#define RAOCP_EVAL_COST 0
+#define RAOCP_EVAL_S0   1
+#define RAOCP_EVAL_BOX  2
+#define RAOCP_EVAL_DYN  3
+#define RAOCP_EVAL_N    4
+int raocp_evaluate(raocp_ctx* ctx, const double* z, int flags, double* out /*[RAOCP_EVAL_N]*/,
+                   double* node_values /*[n] or NULL*/);
+/* The same four values for the final primal of every instance of the last raocp_cp_batch_run /
+ * raocp_cp_batch_mpc, x0 being the state the instance's last solve was solved from. One launch,
+ * one workgroup per instance (k_eval_batch) when k_cpb ran the batch; the kernels of
+ * raocp_evaluate over each stored primal when it ran as sequential solves, with the same
+ * values. Errors: RAOCP_ERR_ARG for a NULL out; RAOCP_ERR_STATE before any batch or on a
+ * sharded context. kernel_info op 18 names the kernel. */
+int raocp_cp_batch_evaluate(raocp_ctx* ctx, double* out /*[B][RAOCP_EVAL_N]*/);
+
 /* Benchmark helpers (bench.py): raocp_cp_bench runs exactly `iters` CP iterations
  * (tol = 0) from (x0 at node 0, zeros) / 0 on the device, graph-replayed (whole
  * batches of 24 iterations, then one remainder batch), without host syncs inside;
@@ -258,7 +299,10 @@ int raocp_cp_batch_mpc(raocp_ctx* ctx, int B, int T, const double* x0 /*[B][nx]*
 int raocp_cp_prepare(raocp_ctx* ctx, const double* x0, int iters, double alpha);
 int raocp_cp_bench(raocp_ctx* ctx, const double* x0, int iters, double alpha, float* ms);
 /* Time `reps` back-to-back launches of L (op=0) or L^T (op=1) on device-resident
- * vectors with HIP events on the context's stream; returns average ms per launch. */
+ * vectors with HIP events on the context's stream; returns average ms per launch.
+ * op=17: the launches of one raocp_evaluate on the context's current primal (k_eval_nodes and
+ * the sweep), reps evaluations between the two events; needs an initial state and leaves the
+ * context as it was. */
 int raocp_op_bench(raocp_ctx* ctx, int op, int reps, float* ms_per_launch);
 /* The same for L (op 0) / L^T (op 1) with the launches cycling over `nsets` (<= 16) freshly
  * allocated input / output buffer pairs, so that a working set beyond the 256 MiB Infinity

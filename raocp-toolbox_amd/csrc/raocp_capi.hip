@@ -9,6 +9,7 @@
 #include "raocp_cp4.h"
 #include "raocp_cp5.h"
 #include "raocp_cpb.h"
+#include "raocp_eval.h"
 #include "../../include/raocp_hip.h"
 
 #include <dlfcn.h>
@@ -1105,6 +1106,10 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             return cpb_on(c) ? raocp::cpb_name(c->f32, raocp::cpb_tab_bytes(c->dev, c->f32) > 0) : "";
         case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
             return cpb_on(c) ? raocp::mpc_step_name(c->f32) : "";
+        case 17:  // the kernels of raocp_evaluate and its number of sweep launches
+            return raocp::eval_name(c->f32, (int)raocp::eval_sweep_plan(c->stage_ptr).size());
+        case 18:  // the kernel of raocp_cp_batch_evaluate: the last batch's own form, else what a batch would run
+            return (c->bt.B >= 1 ? c->bt.kernel : cpb_on(c)) ? raocp::eval_batch_name(c->f32) : "";
         case 10: {  // a shard launches the fused forms k_cp5 and k_cp3 twice (launch_cp_fused)
             const bool sh = c->sh_S > 0;
             switch (c->path.cp) {
@@ -1480,7 +1485,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16 && op != 18) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }
@@ -1901,6 +1906,7 @@ int batch_run_seq(raocp_ctx* c, int B, const double* x0, const double* z0, const
     bt.hz.assign((size_t)B * c->P, 0.0);
     bt.he.assign((size_t)B * c->D, 0.0);
     bt.hu0.assign((size_t)B * c->nu, 0.0);
+    bt.hx0.assign(x0, x0 + (size_t)B * c->nx);
     bt.fk.assign(B, 0);
     int rc = RAOCP_OK;
     for (int b = 0; b < B && rc == RAOCP_OK; ++b) {
@@ -2073,6 +2079,7 @@ int batch_mpc_seq(raocp_ctx* c, int B, int T, const double* x0, const int* scen,
     std::vector<double> xc(x0, x0 + (size_t)B * nx), Z((size_t)B * P, 0.0), E((size_t)B * D, 0.0), U0((size_t)B * nu, 0.0);
     std::vector<int> frz(B, -1), act, st(B), itv(B);
     std::vector<double> ax, az, ae, eh((size_t)B * rows * 3), dh((size_t)B * rows * 3);
+    std::vector<double> xs(xc);  // the state each instance's last solve was solved from
     for (int b = 0; b < B; ++b) std::copy(x0 + (size_t)b * nx, x0 + (size_t)(b + 1) * nx, X + (size_t)b * (T + 1) * nx);
     auto blank = [&](int b, int t) {
         const size_t bt_ = (size_t)b * T + t;
@@ -2112,6 +2119,7 @@ int batch_mpc_seq(raocp_ctx* c, int B, int T, const double* x0, const int* scen,
         for (int q = 0; q < nA; ++q) {
             const int b = act[q];
             const size_t bt_ = (size_t)b * T + t;
+            std::copy(xc.begin() + (size_t)b * nx, xc.begin() + (size_t)(b + 1) * nx, xs.begin() + (size_t)b * nx);
             std::copy(bt.hz.begin() + q * P, bt.hz.begin() + (q + 1) * P, Z.begin() + b * P);
             std::copy(bt.he.begin() + q * D, bt.he.begin() + (q + 1) * D, E.begin() + b * D);
             std::copy(bt.hu0.begin() + (size_t)q * nu, bt.hu0.begin() + (size_t)(q + 1) * nu, U0.begin() + (size_t)b * nu);
@@ -2153,15 +2161,120 @@ int batch_mpc_seq(raocp_ctx* c, int B, int T, const double* x0, const int* scen,
     bt.hz = Z;
     bt.he = E;
     bt.hu0 = U0;
+    bt.hx0 = xs;
     mpc_final_k(bt.fk, B, T, iters);
     bt.B = B;
     bt.kernel = false;
     return RAOCP_OK;
 }
 
+// ---- evaluation of a primal (raocp_evaluate, raocp_cp_batch_evaluate; raocp_eval.hip)
+
+int eval_ensure(raocp_ctx* c) {
+    if (c->eval_buf) return RAOCP_OK;
+    c->eval_plan = raocp::eval_sweep_plan(c->stage_ptr);
+    c->eval_grid = raocp::eval_nodes_grid(c->dev);
+    return c->alloc(&c->eval_buf, (size_t)2 * c->n + (size_t)2 * c->eval_grid + RAOCP_EVAL_N + c->nx);
+}
+double* eval_x0_slot(raocp_ctx* c) { return c->eval_buf + (size_t)2 * c->n + (size_t)2 * c->eval_grid + RAOCP_EVAL_N; }
+
+// the single-solve kernels over a device primal and a device initial state of the context's
+// scalar type; the four results (and V_i of every node) to the host
+raocp::EvalArg eval_arg(raocp_ctx* c, const void* dz, const void* dx0) {
+    raocp::EvalArg a{};
+    a.z = dz;
+    a.x0 = dx0;
+    a.w = c->eval_buf;
+    a.val = a.w + c->n;
+    a.part = a.val + c->n;
+    a.out = a.part + (size_t)2 * c->eval_grid;
+    a.grid = c->eval_grid;
+    a.w_stride = raocp::tstride(c->KP);
+    return a;
+}
+int eval_run(raocp_ctx* c, const void* dz, const void* dx0, double* out, double* node_values) {
+    const raocp::EvalArg a = eval_arg(c, dz, dx0);
+    HIPCHK(raocp::eval_launch(c->dev, a, c->eval_plan, c->f32, c->stream));
+    HIPCHK(hipMemcpyAsync(out, a.out, RAOCP_EVAL_N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (node_values)
+        HIPCHK(hipMemcpyAsync(node_values, a.val, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RAOCP_OK;
+}
+
+// every instance of a batch k_cpb ran, inside the slabs: one launch
+int batch_eval_kernel(raocp_ctx* c, double* out) {
+    const auto& bt = c->bt;
+    const int B = bt.B;
+    const bool ldsw = raocp::eval_batch_w_in_lds(c->dev);
+    const size_t n_out = (size_t)B * RAOCP_EVAL_N, n_scr = ldsw ? 0 : (size_t)B * c->n;
+    char* blk = nullptr;  // [out | scratch | zsel]
+    HIPCHK(hipMalloc((void**)&blk, (n_out + n_scr) * sizeof(double) + (size_t)B * sizeof(int)));
+    std::vector<int> zsel(B);
+    for (int b = 0; b < B; ++b) zsel[b] = (bt.fk[b] + 1) % 3;  // the primal raocp_cp_batch_get reads
+    raocp::EvalBatchArg a{};
+    a.slab = bt.slab;
+    a.lay = bt.lay;
+    a.out = (double*)blk;
+    a.scratch = a.out + n_out;
+    a.zsel = (const int*)(a.scratch + n_scr);
+    a.B = B;
+    a.w_stride = raocp::tstride(c->KP);
+    hipError_t e = hipMemcpyAsync((void*)a.zsel, zsel.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = raocp::eval_batch_launch(c->dev, a, c->f32, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, a.out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(blk);
+    if (e != hipSuccess) return fail(RAOCP_ERR_HIP, std::string("batch evaluation: ") + hipGetErrorString(e));
+    return RAOCP_OK;
+}
+
+// every instance of a batch that ran as sequential solves: the single-solve kernels over each
+// stored final primal (staged in tmpP; the context's iterate and initial state are not touched)
+int batch_eval_seq(raocp_ctx* c, double* out) {
+    const auto& bt = c->bt;
+    if (bt.hx0.size() != (size_t)bt.B * c->nx || bt.hz.size() != (size_t)bt.B * c->P)
+        return fail(RAOCP_ERR_STATE, "the last batch kept no final primals");
+    int rc;
+    if ((rc = eval_ensure(c))) return rc;
+    for (int b = 0; b < bt.B; ++b) {
+        if ((rc = copy_in(c, c->tmpP, bt.hz.data() + (size_t)b * c->P, (size_t)c->P, 0))) return rc;
+        if ((rc = copy_in(c, eval_x0_slot(c), bt.hx0.data() + (size_t)b * c->nx, (size_t)c->nx, 0))) return rc;
+        if ((rc = eval_run(c, c->tmpP, eval_x0_slot(c), out + (size_t)b * RAOCP_EVAL_N, nullptr))) return rc;
+    }
+    return RAOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int raocp_evaluate(raocp_ctx* c, const double* z, int flags, double* out, double* node_values) {
+    DevGuard dg_(c);
+    SweepLock sl_(c);
+    if (!c || !out) return fail(RAOCP_ERR_ARG, "null argument");
+    if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "the evaluation is not available on a sharded context");
+    if (!c->has_x0) return fail(RAOCP_ERR_STATE, "no initial state has been set");
+    int rc;
+    if ((rc = eval_ensure(c))) return rc;
+    const void* dz = c->cur_z;
+    if (z && (flags & RAOCP_DEVICE_PTR)) {
+        dz = z;
+    } else if (z) {
+        if ((rc = copy_in(c, c->tmpP, z, (size_t)c->P, 0))) return rc;
+        dz = c->tmpP;
+    }
+    return eval_run(c, dz, c->x0, out, node_values);
+}
+
+int raocp_cp_batch_evaluate(raocp_ctx* c, double* out) {
+    DevGuard dg_(c);
+    SweepLock sl_(c);
+    if (!c || !out) return fail(RAOCP_ERR_ARG, "null argument");
+    if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "the evaluation is not available on a sharded context");
+    if (c->bt.B < 1) return fail(RAOCP_ERR_STATE, "no batch has been run");
+    return c->bt.kernel ? batch_eval_kernel(c, out) : batch_eval_seq(c, out);
+}
 
 int raocp_cp_batch_run(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
                        double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist) {
@@ -2609,6 +2722,28 @@ int raocp_op_bench(raocp_ctx* c, int op, int reps, float* ms_per_launch) {
     DevGuard dg_(c);
     SweepLock sl_(c);
     if (!c || reps < 1 || !ms_per_launch) return fail(RAOCP_ERR_ARG, "bad argument");
+    if (op == 17) {
+        // the launches of one raocp_evaluate on the context's current primal, reps times, between two
+        // events; nothing of the context moves (no random inputs, no control block)
+        if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "the evaluation is not available on a sharded context");
+        if (!c->has_x0) return fail(RAOCP_ERR_STATE, "no initial state has been set");
+        if (int re = eval_ensure(c)) return re;
+        const raocp::EvalArg a = eval_arg(c, c->cur_z, c->x0);
+        HIPCHK(raocp::eval_launch(c->dev, a, c->eval_plan, c->f32, c->stream));  // warm-up
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, c->stream));
+        for (int i = 0; i < reps; ++i) HIPCHK(raocp::eval_launch(c->dev, a, c->eval_plan, c->f32, c->stream));
+        HIPCHK(hipEventRecord(e1, c->stream));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        *ms_per_launch = ms / reps;
+        return RAOCP_OK;
+    }
     if (op == 0 || op == 1)
         if (int ra = ell_available(c)) return ra;
     // random inputs (seed 1), resident in HBM

@@ -218,7 +218,14 @@ struct raocp_ctx {
         double* u0 = nullptr;
         std::vector<int> fk;         // final_k per instance
         std::vector<double> hz, he, hu0;  // the sequential solves' final iterates and first inputs
+        std::vector<double> hx0;     // ... and the state each instance's last solve was solved from
     } bt;
+    // evaluation of a primal (raocp_evaluate, raocp_eval.hip): the sweep's launch plan and one
+    // device block [w (n) | val (n) | part (2 per workgroup of the node pass) | out (4) | x0 of a
+    // stored primal (nx)], set up at the first evaluation
+    std::vector<raocp::EvalLaunch> eval_plan;
+    double* eval_buf = nullptr;
+    int eval_grid = 0;
     // closed-loop simulation of a batch (raocp_cp_batch_mpc): the plant tables of the root's
     // children (host copies from create; A | B uploaded at the first simulation in the
     // context's scalar type) and the

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "raocp_group_cp_run_warm",
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
     "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs", "raocp_cp_batch_mpc",
+    "raocp_evaluate", "raocp_cp_batch_evaluate",
 ]
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -101,6 +102,8 @@ def load_library():
         "raocp_cp_batch_first_inputs": (c_int, [vp, vp]),
         "raocp_cp_batch_mpc": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_double, c_double, c_int,
                                        vp, vp, vp, vp, vp, vp]),
+        "raocp_evaluate": (c_int, [vp, vp, c_int, vp, vp]),
+        "raocp_cp_batch_evaluate": (c_int, [vp, vp]),
         "raocp_cp_prepare": (c_int, [vp, vp, c_int, c_double]),
         "raocp_cp_bench": (c_int, [vp, vp, c_int, c_double, ctypes.POINTER(ctypes.c_float)]),
         "raocp_op_bench": (c_int, [vp, c_int, c_int, ctypes.POINTER(ctypes.c_float)]),
@@ -413,6 +416,26 @@ class NativeContext:
             _ptr(X), _ptr(U), _ptr(cost), _ptr(status), _ptr(iters), _ptr(err)))
         self._batch_B = B
         return X, U, cost, status.astype(np.int64), iters.astype(np.int64), err
+
+    # ---- evaluation of a primal (include/raocp_hip.h raocp_evaluate)
+    def evaluate(self, z=None, node_values=False):
+        """(cost, s_0, box violation, dynamics residual) of the flat primal z (None: the context's
+        current primal) against the initial state that was set last, as a (4,) array; with
+        node_values=True also the (n,) array of every node's cost-to-go (leaves: the terminal
+        cost). Nothing of the context changes."""
+        out = np.zeros(4)
+        zp = None if z is None else _ptr(self._vec(z, self.P))
+        vals = np.zeros(self._packed.n) if node_values else None
+        self._check(self._lib.raocp_evaluate(self._h, zp, 0, _ptr(out), None if vals is None else _ptr(vals)))
+        return (out, vals) if node_values else out
+
+    def cp_batch_evaluate(self):
+        """(B, 4): the four values of evaluate() for the final primal of every instance of the last
+        batch (cp_batch_run / cp_batch_mpc), each against the state its last solve started from."""
+        B = getattr(self, "_batch_B", 0)
+        out = np.zeros((max(B, 1), 4))
+        self._check(self._lib.raocp_cp_batch_evaluate(self._h, _ptr(out)))
+        return out[:B]
 
     def cp_prepare(self, iters, x0=None, alpha=0.0):
         """Capture the CP graphs an `iters`-iteration cp_bench launches and, given x0, reset

@@ -20,7 +20,8 @@ import raocp.core.cache as cache
 import raocp.core.operators as ops
 import raocp.core.raocp_spec as spec
 
-__all__ = ["Solver", "normalise_initial_states", "normalise_scenarios", "sample_scenarios", "BatchSimulation"]
+__all__ = ["Solver", "normalise_initial_states", "normalise_scenarios", "sample_scenarios", "BatchSimulation",
+           "Evaluation"]
 
 
 def normalise_initial_states(initial_states, nx):
@@ -71,6 +72,27 @@ class BatchSimulation:
         self.iterations = iterations
         self.errors = errors
         self.scenarios = scenarios
+
+
+class Evaluation:
+    """What a computed policy costs and how far it is from feasible (Solver.evaluate /
+    evaluate_batch): cost, the nested-AVaR objective V_0 of the primal's states and inputs;
+    epigraph, the primal's own s_0 (equal to the cost only at convergence); box_violation, the
+    largest amount by which an active box is missed (0 without boxes); dynamics_residual, the
+    largest |x_0 - x0| and |x_j - A_j x_anc(j) - B_j u_anc(j)| entry; node_values, None or the
+    (n,) cost-to-go of every node (leaves: the terminal cost). Floats for one solve, (B,) arrays
+    for a batch."""
+
+    def __init__(self, cost, epigraph, box_violation, dynamics_residual, node_values=None):
+        self.cost = cost
+        self.epigraph = epigraph
+        self.box_violation = box_violation
+        self.dynamics_residual = dynamics_residual
+        self.node_values = node_values
+
+    def __repr__(self):
+        return (f"Evaluation(cost={self.cost!r}, epigraph={self.epigraph!r}, box_violation={self.box_violation!r}, "
+                f"dynamics_residual={self.dynamics_residual!r})")
 
 
 class Solver:
@@ -260,6 +282,19 @@ class Solver:
 
     def batch_first_inputs(self):
         return self.__cache.native.cp_batch_first_inputs()
+
+    # ----- evaluation of the computed policy (extension)
+    def evaluate(self, node_values=False):
+        """The Evaluation of the primal the last chock left, against its initial state."""
+        res = self.__cache.native.evaluate(None, node_values=node_values)
+        out, vals = res if node_values else (res, None)
+        return Evaluation(float(out[0]), float(out[1]), float(out[2]), float(out[3]), vals)
+
+    def evaluate_batch(self):
+        """The Evaluation of every instance of the last chock_batch or simulate_batch (there: of
+        each instance's last solve, as batch_primal_flat describes it); the fields are (B,) arrays."""
+        out = self.__cache.native.cp_batch_evaluate()
+        return Evaluation(out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy())
 
     # ----- outputs (solver.py:173-253)
     @property
