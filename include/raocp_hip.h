@@ -152,7 +152,9 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * the number of sweep launches ("<float>" on an fp32 context); op 18: the kernel of
  * raocp_cp_batch_evaluate, "k_eval_batch<double>" / "k_eval_batch<float>", or "" when the batch
  * evaluation runs the kernels of op 17 over each stored primal (after a batch: by how that batch
- * ran; before any: by how one would run now, as op 13 reports it);
+ * ran; before any: by how one would run now, as op 13 reports it); op 19: the kernel of
+ * raocp_cp_batch_run_aa, "k_cpa<true>" / "k_cpa<false>" (the shared tables staged in LDS or
+ * not), or "" on a context that call refuses (fp32, sharded, or one k_cpb does not cover);
  * written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
@@ -219,8 +221,37 @@ int raocp_cp_batch_run(raocp_ctx* ctx, int B, const double* x0 /*[B][nx]*/,
                        int max_iters, double tol, double alpha,
                        int* status /*[B]*/, int* iters /*[B]*/,
                        double* err_hist /*[B][max_iters+1][3]*/, double* delta_hist);
+/* raocp_cp_batch_run with Anderson acceleration of memory accel = m, 1 <= m <= 8 (kernel k_cpa,
+ * one workgroup per instance). With v = (z, eta), g_k = T(v_k) one CP iteration
+ * and r_k = g_k - v_k: the last m difference columns dG, dR of the pairs (g_k, r_k) are kept;
+ * after iteration k with (k + 1) % accel_every == 0 and at least one column,
+ * gamma = (dR'dR + accel_reg (tr / j) I)^-1 dR'r_k by Cholesky in double and the next iterate is
+ * the proposal g_k - dG gamma. The iteration after it is the trial: accepted when
+ * |T(v^) - v^|_2 <= accel_safeguard |r_k|_2, else the history is cleared and the solve goes on
+ * from g_k. A non-positive pivot or a non-finite gamma clears the history (no proposal). Every
+ * iteration, trials included, writes its history row and counts against max_iters; a rejected
+ * trial never ends the solve through tol. Inputs, outputs and the follow-up calls
+ * (raocp_cp_batch_get, _first_inputs, _evaluate) are those of raocp_cp_batch_run; z0 / eta0
+ * start with an empty history. Errors: as raocp_cp_batch_run, RAOCP_ERR_ARG for accel outside
+ * 1 .. 8, accel_every < 1 or a negative accel_reg / accel_safeguard, RAOCP_ERR_STATE on an fp32
+ * context, a sharded one or one k_cpb does not cover (there is no sequential form). kernel_info
+ * op 19 names the kernel. */
+int raocp_cp_batch_run_aa(raocp_ctx* ctx, int B, const double* x0, const double* z0, const double* eta0,
+                          int max_iters, double tol, double alpha, int accel, int accel_every, double accel_reg,
+                          double accel_safeguard, int* status, int* iters, double* err_hist, double* delta_hist);
+/* The acceleration's log of instance b of the last raocp_cp_batch_run_aa: iters[b] records of 12
+ * doubles, one per history row: code (0 plain, 1 proposal made, 2 trial accepted, 3 trial
+ * rejected, 4 solve refused), j (columns when the solve ran, else after the push), prop (what
+ * followed in this iteration: 0 nothing, 1 a proposal, 2 a refused solve; it tells what an
+ * accepted trial, code 2, went on to do), |r_k|_2, gamma[8] (column order, oldest first, zero
+ * beyond j). RAOCP_ERR_STATE when the last batch was not accelerated. */
+int raocp_cp_batch_aa_log(raocp_ctx* ctx, int b, double* out /*[iters[b]][12]*/);
 /* The final primal / dual of instance b of the last batch, in the reference's flat order. */
 int raocp_cp_batch_get(raocp_ctx* ctx, int b, double* z /*[P]*/, double* eta /*[D]*/);
+/* The pair (z, eta) that instance b's last iteration was computed from (the final iterate is one
+ * CP iteration of it, and the last history row is that iteration's): after a batch a kernel ran
+ * (k_cpb, k_cpa); RAOCP_ERR_STATE after the sequential solves, which do not keep it. */
+int raocp_cp_batch_get_prev(raocp_ctx* ctx, int b, double* z /*[P]*/, double* eta /*[D]*/);
 /* The root's input u_0 of every instance's final primal (what an MPC loop applies). */
 int raocp_cp_batch_first_inputs(raocp_ctx* ctx, double* u0 /*[B][nu]*/);
 

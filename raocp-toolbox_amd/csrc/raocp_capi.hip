@@ -1015,6 +1015,11 @@ void batch_free(raocp_ctx* c) {
     if (bt.done) (void)hipFree(bt.done);
     if (bt.hist) (void)hipFree(bt.hist);
     if (bt.u0) (void)hipFree(bt.u0);
+    if (bt.aslab) (void)hipFree(bt.aslab);
+    if (bt.alog) (void)hipFree(bt.alog);
+    bt.aslab = bt.alog = nullptr;
+    bt.a_m = 0;
+    bt.a_rows = 0;
     bt.slab = nullptr;
     bt.hist = bt.u0 = nullptr;
     bt.ctl = nullptr;
@@ -1104,6 +1109,8 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             return std::string("leaf_pf=") + (c->cp5_lpf ? "1" : "0");
         case 13:  // the batched CP kernel, when raocp_cp_batch_run launches it ("" otherwise)
             return cpb_on(c) ? raocp::cpb_name(c->f32, raocp::cpb_tab_bytes(c->dev, c->f32) > 0) : "";
+        case 19:  // the accelerated batch kernel of raocp_cp_batch_run_aa ("" where it refuses)
+            return cpb_on(c) && !c->f32 ? raocp::cpa_name(raocp::cpb_tab_bytes(c->dev, false) > 0) : "";
         case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
             return cpb_on(c) ? raocp::mpc_step_name(c->f32) : "";
         case 17:  // the kernels of raocp_evaluate and its number of sweep launches
@@ -1485,7 +1492,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16 && op != 18) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16 && op != 18 && op != 19) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }
@@ -1828,12 +1835,41 @@ raocp::CpbArg batch_arg(raocp_ctx* c, int B, size_t rows) {
     return a;
 }
 
+// the options of an accelerated batch (raocp_cp_batch_run_aa)
+struct AaOpt {
+    int m, every;
+    double reg, safeguard;
+};
+
+// the acceleration's slabs and log for the batch buffers batch_ensure has just sized; cleared,
+// so every instance starts with an empty history
+int batch_ensure_aa(raocp_ctx* c, int B, int m) {
+    auto& bt = c->bt;
+    if (bt.a_m != m || bt.a_rows != bt.hist_rows) {
+        if (bt.aslab) (void)hipFree(bt.aslab);
+        if (bt.alog) (void)hipFree(bt.alog);
+        bt.aslab = bt.alog = nullptr;
+        bt.a_m = 0;
+        bt.alay = raocp::cpa_layout(c->dev, m);
+        HIPCHK(hipMalloc((void**)&bt.aslab, (size_t)B * bt.alay.stride * sizeof(double)));
+        HIPCHK(hipMalloc((void**)&bt.alog, (size_t)B * bt.hist_rows * raocp::kAaRec * sizeof(double)));
+        bt.a_m = m;
+        bt.a_rows = bt.hist_rows;
+    }
+    HIPCHK(hipMemsetAsync(bt.aslab, 0, (size_t)B * bt.alay.stride * sizeof(double), c->stream));
+    return RAOCP_OK;
+}
+
+// aa: nullptr runs k_cpb; else k_cpa with these options
 int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
-                     double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist) {
+                     double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist,
+                     const AaOpt* aa = nullptr) {
     auto& bt = c->bt;
     const size_t rows = (size_t)max_iters + 1;
     int rc;
+    bt.accel = false;
     if ((rc = batch_ensure(c, B, rows))) return rc;
+    if (aa && (rc = batch_ensure_aa(c, B, aa->m))) return rc;
     const raocp::CpbSlab& L = bt.lay;
     HIPCHK(hipMemsetAsync(bt.slab, 0, (size_t)B * L.stride * c->wsz, c->stream));
     HIPCHK(hipMemsetAsync(bt.done, 0, (size_t)B * sizeof(int), c->stream));
@@ -1856,8 +1892,17 @@ int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, co
     std::vector<int> hd((size_t)B, 0);
     const long launches = (long)(rows + a.chunk - 1) / a.chunk + 1;  // every instance ends within rows iterations
     bool all = false;
+    raocp::CpaArg ca{};
+    if (aa) {
+        ca.slab = bt.aslab;
+        ca.lay = bt.alay;
+        ca.log = bt.alog;
+        ca.every = aa->every;
+        ca.reg = aa->reg;
+        ca.safeguard = aa->safeguard;
+    }
     for (long l = 0; l < launches && !all; ++l) {
-        HIPCHK(raocp::cpb_launch(c->dev, a, c->f32, c->stream));
+        HIPCHK(aa ? raocp::cpa_launch(c->dev, a, ca, c->stream) : raocp::cpb_launch(c->dev, a, c->f32, c->stream));
         HIPCHK(hipMemcpyAsync(hd.data(), bt.done, hd.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         all = std::all_of(hd.begin(), hd.end(), [](int v) { return v != 0; });
@@ -1881,6 +1926,8 @@ int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, co
     }
     bt.B = B;
     bt.kernel = true;
+    bt.accel = aa != nullptr;
+    bt.a_log_rows = rows;
     return RAOCP_OK;
 }
 
@@ -2285,8 +2332,40 @@ int raocp_cp_batch_run(raocp_ctx* c, int B, const double* x0, const double* z0, 
     if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
     if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "batched solves are not available on a sharded context");
     c->bt.B = 0;
+    c->bt.accel = false;
     if (cpb_on(c)) return batch_run_kernel(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist);
     return batch_run_seq(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist);
+}
+
+int raocp_cp_batch_run_aa(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
+                          double tol, double alpha, int accel, int accel_every, double accel_reg, double accel_safeguard,
+                          int* status, int* iters, double* err_hist, double* delta_hist) {
+    DevGuard dg_(c);
+    if (!c || !x0 || !status || !iters || !err_hist || !delta_hist) return fail(RAOCP_ERR_ARG, "null argument");
+    if (B < 1 || B > 4096) return fail(RAOCP_ERR_ARG, "batch size must be in 1 .. 4096");
+    if ((z0 == nullptr) != (eta0 == nullptr)) return fail(RAOCP_ERR_ARG, "z0 and eta0 are given together");
+    if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
+    if (accel < 1 || accel > raocp::kAaMaxM) return fail(RAOCP_ERR_ARG, "accel must be in 1 .. 8");
+    if (accel_every < 1) return fail(RAOCP_ERR_ARG, "accel_every must be >= 1");
+    if (!(accel_reg >= 0.0) || !(accel_safeguard >= 0.0)) return fail(RAOCP_ERR_ARG, "accel_reg and accel_safeguard must be >= 0");
+    if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "batched solves are not available on a sharded context");
+    if (c->f32) return fail(RAOCP_ERR_STATE, "accelerated batched solves are not available on an fp32 context");
+    if (!cpb_on(c)) return fail(RAOCP_ERR_STATE, "accelerated batched solves need the batch kernel, which does not cover this context");
+    c->bt.B = 0;
+    c->bt.accel = false;
+    const AaOpt aa{accel, accel_every, accel_reg, accel_safeguard};
+    return batch_run_kernel(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist, &aa);
+}
+
+int raocp_cp_batch_aa_log(raocp_ctx* c, int b, double* out) {
+    DevGuard dg_(c);
+    if (!c || !out) return fail(RAOCP_ERR_ARG, "null argument");
+    const auto& bt = c->bt;
+    if (bt.B < 1 || !bt.accel) return fail(RAOCP_ERR_STATE, "no accelerated batch has been run");
+    if (b < 0 || b >= bt.B) return fail(RAOCP_ERR_ARG, "instance index out of range");
+    const size_t n = (size_t)(bt.fk[b] + 1) * raocp::kAaRec;
+    HIPCHK(hipMemcpy(out, bt.alog + (size_t)b * bt.a_log_rows * raocp::kAaRec, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RAOCP_OK;
 }
 
 int raocp_cp_batch_get(raocp_ctx* c, int b, double* z, double* eta) {
@@ -2307,6 +2386,22 @@ int raocp_cp_batch_get(raocp_ctx* c, int b, double* z, double* eta) {
     int rc;
     if ((rc = copy_out(c, z, (const double*)(slab + (size_t)bt.lay.z[(fk + 1) % 3] * w), (size_t)c->P, 0))) return rc;
     return copy_out(c, eta, (const double*)(slab + (size_t)bt.lay.e[(fk + 1) % 2] * w), (size_t)c->D, 0);
+}
+
+int raocp_cp_batch_get_prev(raocp_ctx* c, int b, double* z, double* eta) {
+    DevGuard dg_(c);
+    if (!c || !z || !eta) return fail(RAOCP_ERR_ARG, "null argument");
+    const auto& bt = c->bt;
+    if (bt.B < 1) return fail(RAOCP_ERR_STATE, "no batch has been run");
+    if (b < 0 || b >= bt.B) return fail(RAOCP_ERR_ARG, "instance index out of range");
+    if (!bt.kernel) return fail(RAOCP_ERR_STATE, "the sequential solves keep no previous iterate");
+    // iteration final_k read Z[final_k % 3], E[final_k % 2] and wrote the other buffers
+    const size_t w = (size_t)c->wsz;
+    const char* slab = bt.slab + (size_t)b * bt.lay.stride * w;
+    const int fk = bt.fk[b];
+    int rc;
+    if ((rc = copy_out(c, z, (const double*)(slab + (size_t)bt.lay.z[fk % 3] * w), (size_t)c->P, 0))) return rc;
+    return copy_out(c, eta, (const double*)(slab + (size_t)bt.lay.e[fk % 2] * w), (size_t)c->D, 0);
 }
 
 int raocp_cp_batch_first_inputs(raocp_ctx* c, double* u0) {
@@ -2336,6 +2431,7 @@ int raocp_cp_batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* 
             return fail(RAOCP_ERR_ARG, "scenario entry " + std::to_string(scen[q]) + " is not a child of the root (0 .. " +
                                            std::to_string(nc - 1) + ")");
     c->bt.B = 0;
+    c->bt.accel = false;
     if (cpb_on(c)) return batch_mpc_kernel(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
     return batch_mpc_seq(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
 }

@@ -5,6 +5,8 @@
 
 #include "raocp_common.h"
 #include "raocp_cpb_layout.h"
+#include "raocp_cpa_layout.h"
+#include "raocp_aa_ops.h"
 
 namespace raocp {
 
@@ -52,6 +54,20 @@ struct MpcArg {
     int warm;            // the next solve starts from this step's final iterate (else from zero)
     int last;            // t == T - 1: record only, the slab keeps the last solve
 };
+
+// k_cpa: k_cpb's iteration with Anderson acceleration (fp64 only). The CP iterate stays in the
+// CpbSlab of CpbArg; the acceleration's history and state live in a second slab per instance.
+struct CpaArg {
+    double* slab;        // [B] CpaSlab
+    CpaSlab lay;
+    double* log;         // [B][hist_rows][kAaRec] one record per iteration
+    int every;           // a proposal after iteration k when (k + 1) % every == 0
+    double reg;          // relative Tikhonov term of the normal equations
+    double safeguard;    // a trial is accepted when |T(v^) - v^|_2 <= safeguard |r_k|_2
+};
+CpaSlab cpa_layout(const Dev& p, int m);
+hipError_t cpa_launch(const Dev& p, const CpbArg& a, const CpaArg& aa, hipStream_t stream);
+const char* cpa_name(bool lds_tabs);
 
 // f32: the context's scalar type is float (its Dev tables hold floats)
 CpbSlab cpb_layout(const Dev& p, bool f32);

@@ -48,6 +48,8 @@ using cg = const __attribute__((address_space(1))) T*;
 template <class T>
 using cl = const __attribute__((address_space(3))) T*;
 typedef __attribute__((address_space(1))) const int glbi;
+template <class T>
+using lds = __attribute__((address_space(3))) T;
 
 constexpr __host__ __device__ int rup_(int a, int b) { return (a + b - 1) / b * b; }
 // the row strides of the dynamics tables (raocp_dyn.hip tstride)
@@ -627,6 +629,248 @@ __global__ void __launch_bounds__(kCpbBlock) k_cpb(Dev p, CpbArg a) {
     }
 }
 
+// ---- k_cpa: k_cpb's iteration with Anderson acceleration, fp64 only.
+// With v = (z, eta), g_k = T(v_k) the iteration above and r_k = g_k - v_k, after the phases of
+// iteration k:
+//   A. one pass over the P + D entries: r_k, the new difference column (g_k - g_prev,
+//      r_k - r_prev) into the ring slot `head` when a previous pair is held, the pair itself, and
+//      per lane the partial sums of |r_k|^2, of b = dR' r_k and of the new row of G = dR' dR
+//      (double; a wave shuffle tree, then the waves in index order by thread 0)
+//   B. thread 0: the history row and the stopping test as in k_cpb; a pending trial is accepted
+//      when |r_k|_2 <= safeguard |r_saved|_2, else rejected (history cleared, g_saved comes back;
+//      a rejected trial does not stop on the tolerance); otherwise the push is committed and,
+//      when (k + 1) % every == 0, gamma = (G + reg (tr G / j) I)^-1 b (aa_solve); the log record
+//   C. a proposal: g_k is saved and v^ = g_k - dG gamma takes its place in Z[(k + 1) % 3],
+//      E[(k + 1) % 2]; a rejection: the saved g_k goes there. Either way the half step
+//      Z[(k + 2) % 3] is computed again from that pair, as the solve's first half step is.
+// The pass writes only the acceleration slab, so what it leaves after the iteration that ends
+// the solve, or before a rejection clears the history, is never read. All state between two
+// iterations is in the slabs and Ctl: a launch may end between a proposal and its trial.
+template <class T, class PT>
+__device__ __forceinline__ void cpa_body(const Dev& p, const CpbArg& a, const CpaArg& aa, const Tabs<PT>& tb, int b) {
+    static_assert(std::is_same<T, double>::value, "k_cpa is fp64 only");
+    constexpr int M8 = kAaMaxM, NW = kCpbBlock / 64, ND = 2 * M8 + 1;
+    __shared__ T s_red[6][NW];
+    __shared__ double s_dot[ND][NW];
+    __shared__ double s_gam[M8], s_b[M8], s_G[M8 * M8], s_L[M8 * M8];
+    __shared__ int s_slot[M8];
+    __shared__ int s_st[4];   // head, count, have, pending: as thread 0 left them
+    __shared__ int s_ctl[3];  // {done, k, action} of the instance; action 1 proposal, 2 restore
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    Ctl* ctl = a.ctl + b;
+    T* slab = (T*)a.slab + (size_t)b * a.lay.stride;
+    double* hist = a.hist + (size_t)b * a.hist_rows * 6;
+    double* log = aa.log + (size_t)b * a.hist_rows * kAaRec;
+    const CpaSlab& A = aa.lay;
+    double* as = aa.slab + (size_t)b * A.stride;
+    gl<double>* dG = (gl<double>*)(as + A.dg);
+    gl<double>* dR = (gl<double>*)(as + A.dr);
+    gl<double>* pg = (gl<double>*)(as + A.pg);
+    gl<double>* pr = (gl<double>*)(as + A.pr);
+    gl<double>* sg = (gl<double>*)(as + A.sg);
+    double* Gm = as + A.G;
+    CpaState* st = (CpaState*)(as + A.state);
+    const int m = A.m, P = p.P, NE = p.P + p.D;
+    const long vec = A.vec;
+    const T alpha = (T)ctl->alpha;
+    int k = ctl->k;
+    if (tid == 0) {
+        s_st[0] = st->head;
+        s_st[1] = st->count;
+        s_st[2] = st->have;
+        s_st[3] = st->pending;
+    }
+    if (!ctl->pad) {
+        const View<T> v = view_of(slab, a.lay, 0);
+        Maxima<T> none;
+        primal_phase<T, false>(p, tb, v, v.zp, alpha, none, tid, nthr);
+        __syncthreads();
+        if (tid == 0) ctl->pad = 1;
+    }
+    __syncthreads();
+    for (int it = 0; it < a.chunk; ++it) {
+        const View<T> v = view_of(slab, a.lay, k);
+        Maxima<T> mx;
+        bool nan = false;
+        dynamics_phase<T>(p, a, v, v.zp, tid, nthr);
+        dual_phase<T, 1>(p, tb, v, alpha, mx, nan, tid, nthr);
+        __syncthreads();
+        dual_phase<T, 2>(p, tb, v, alpha, mx, nan, tid, nthr);
+        __syncthreads();
+        primal_phase<T, true>(p, tb, v, v.out, alpha, mx, tid, nthr);
+        // A. the acceleration pass
+        const int head = s_st[0], count = s_st[1], have = s_st[2], pending = s_st[3];
+        const int ncol = have ? min(count + 1, m) : count;  // columns once the push is committed
+        double acc[ND];
+        _Pragma("unroll") for (int q = 0; q < ND; ++q) acc[q] = 0.0;
+        for (int e = tid; e < NE; e += nthr) {
+            const double gv = e < P ? v.zp[e] : v.eo[e - P];
+            const double vv = e < P ? v.pz[e] : v.d[e - P];
+            const double r = gv - vv;
+            double drn = 0.0;
+            if (have) {
+                drn = r - pr[e];
+                dR[(size_t)head * vec + e] = drn;
+                dG[(size_t)head * vec + e] = gv - pg[e];
+            }
+            pg[e] = gv;
+            pr[e] = r;
+            acc[2 * M8] = fma(r, r, acc[2 * M8]);
+            _Pragma("unroll") for (int s = 0; s < M8; ++s)
+                if (s < ncol) {
+                    const double c = (have && s == head) ? drn : dR[(size_t)s * vec + e];
+                    acc[M8 + s] = fma(c, r, acc[M8 + s]);
+                    acc[s] = fma(c, drn, acc[s]);
+                }
+        }
+        _Pragma("unroll") for (int q = 0; q < ND; ++q) {
+            double s = acc[q];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            acc[q] = s;
+        }
+        const T mm[6] = {wave_max(mx.m0), wave_max(mx.m1), wave_max(mx.m2),
+                              wave_max(mx.m3), wave_max(mx.m4), wave_max(mx.m5)};
+        if ((tid & 63) == 0) {
+            _Pragma("unroll") for (int q = 0; q < 6; ++q) s_red[q][tid >> 6] = mm[q];
+            _Pragma("unroll") for (int q = 0; q < ND; ++q) s_dot[q][tid >> 6] = acc[q];
+        }
+        const int any_nan = __syncthreads_or(nan ? 1 : 0);
+        // B. the history row, the stopping test and the acceleration's decision
+        if (tid == 0) {
+            T mr[6];
+            _Pragma("unroll") for (int q = 0; q < 6; ++q) {
+                T r = s_red[q][0];
+                for (int w = 1; w < (nthr >> 6); ++w) r = nmx<T>(r, s_red[q][w]);
+                mr[q] = r;
+                hist[(size_t)k * 6 + q] = (double)r;
+            }
+            // the waves' partial sums in index order
+            auto dsum = [&](int q) {
+                double s = s_dot[q][0];
+                for (int w = 1; w < (nthr >> 6); ++w) s += s_dot[q][w];
+                return s;
+            };
+            const double err = (double)nmx<T>(nmx<T>(mr[0], mr[1]), mr[2]);
+            const double rn = sqrt(dsum(2 * M8));
+            for (int i = 0; i < M8; ++i) s_gam[i] = 0.0;
+            int code = 0, prop = 0, action = 0, jlog = 0;
+            int nh = head, nc = count, nhave = have, npend = 0;
+            bool rejected = false;
+            if (pending) {
+                const bool accept = rn <= aa.safeguard * st->rnorm;
+                code = accept ? 2 : 3;
+                rejected = !accept;
+            }
+            if (any_nan) ctl->flags |= 1;
+            const bool stop = k >= ctl->max_iters || any_nan || (!rejected && err <= ctl->tol);
+            if (stop) {
+                ctl->done = 1;
+                ctl->final_k = k;
+                a.done[b] = 1;
+            } else if (rejected) {
+                nh = nc = nhave = 0;
+                action = 2;
+            } else {
+                if (have) {  // the push is committed: the new row and column of G
+                    for (int s = 0; s < ncol; ++s) Gm[head * M8 + s] = Gm[s * M8 + head] = dsum(s);
+                    nh = (head + 1) % m;
+                    nc = ncol;
+                }
+                nhave = 1;
+                jlog = nc;
+                if (nc >= 1 && (k + 1) % aa.every == 0) {
+                    // the columns oldest first
+                    for (int i = 0; i < nc; ++i) {
+                        const int si = (nh - nc + i + m) % m;
+                        s_slot[i] = si;
+                        s_b[i] = dsum(M8 + si);
+                        for (int j = 0; j <= i; ++j) s_G[i * M8 + j] = Gm[si * M8 + s_slot[j]];
+                    }
+                    if (aa_solve(nc, (lds<double>*)s_G, (lds<double>*)s_b, aa.reg, (lds<double>*)s_gam, (lds<double>*)s_L)) {
+                        action = 1;
+                        npend = 1;
+                        st->rnorm = rn;
+                        prop = 1;
+                        if (code == 0) code = 1;
+                    } else {
+                        for (int i = 0; i < M8; ++i) s_gam[i] = 0.0;
+                        nh = nc = nhave = 0;
+                        prop = 2;
+                        if (code == 0) code = 4;
+                    }
+                }
+            }
+            if (!stop) ctl->k = k + 1;
+            double* rec = log + (size_t)k * kAaRec;
+            rec[0] = (double)code;
+            rec[1] = (double)jlog;
+            rec[2] = (double)prop;
+            rec[3] = rn;
+            for (int i = 0; i < M8; ++i) rec[4 + i] = s_gam[i];
+            st->head = s_st[0] = nh;
+            st->count = s_st[1] = nc;
+            st->have = s_st[2] = nhave;
+            st->pending = s_st[3] = npend;
+            s_ctl[0] = stop ? 1 : 0;
+            s_ctl[1] = stop ? k : k + 1;
+            s_ctl[2] = action;
+        }
+        __syncthreads();
+        const int done = s_ctl[0], action = s_ctl[2];
+        k = s_ctl[1];
+        if (done) {
+            if (tid < p.nu) a.u0[(size_t)b * p.nu + tid] = (double)v.zp[p.U0 + tid];
+            break;
+        }
+        // C. the next iterate is not g_k: put it in place and redo the half step from it
+        if (action) {
+            const int nc = s_st[1];
+            for (int e = tid; e < NE; e += nthr) {
+                gl<T>* dst = e < P ? v.zp + e : v.eo + (e - P);
+                if (action == 1) {
+                    const double gv = *dst;
+                    sg[e] = gv;
+                    double s = gv;
+                    for (int i = 0; i < nc; ++i) s = fma(-s_gam[i], dG[(size_t)s_slot[i] * vec + e], s);
+                    *dst = s;
+                } else {
+                    *dst = sg[e];
+                }
+            }
+            __syncthreads();
+            const View<T> vn = view_of(slab, a.lay, k);
+            Maxima<T> none;
+            primal_phase<T, false>(p, tb, vn, vn.zp, alpha, none, tid, nthr);
+            __syncthreads();
+        }
+    }
+}
+
+template <class T, bool LT>
+__global__ void __launch_bounds__(kCpbBlock) k_cpa(Dev p, CpbArg a, CpaArg aa) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_[];
+    const int b = blockIdx.x;
+    if (b >= a.B || a.ctl[b].done) return;  // a finished instance leaves at kernel entry
+    const int nx = p.nx, nu = p.nu;
+    const int nQ = p.nSQ * nx * nx, nR = p.nSR * nu * nu, nP = p.nSP * nx * nx, nBn = p.nBnl * (nx + nu), nBl = p.nBl * nx;
+    if constexpr (LT) {
+        __attribute__((address_space(3))) T* s = (__attribute__((address_space(3))) T*)smem_;
+        const cg<T> src[7] = {(cg<T>)p.SQ, (cg<T>)p.SR, (cg<T>)p.SP, (cg<T>)p.blo_nl, (cg<T>)p.bhi_nl, (cg<T>)p.blo_l, (cg<T>)p.bhi_l};
+        const int cnt[7] = {nQ, nR, nP, nBn, nBn, nBl, nBl};
+        int off[8];
+        off[0] = 0;
+        _Pragma("unroll") for (int t = 0; t < 7; ++t) off[t + 1] = off[t] + cnt[t];
+        _Pragma("unroll") for (int t = 0; t < 7; ++t)
+            for (int e = threadIdx.x; e < cnt[t]; e += blockDim.x) s[off[t] + e] = src[t][e];
+        __syncthreads();
+        const Tabs<cl<T>> tb{s + off[0], s + off[1], s + off[2], s + off[3], s + off[4], s + off[5], s + off[6]};
+        cpa_body<T>(p, a, aa, tb, b);
+    } else {
+        const Tabs<cg<T>> tb{(cg<T>)p.SQ, (cg<T>)p.SR, (cg<T>)p.SP, (cg<T>)p.blo_nl, (cg<T>)p.bhi_nl, (cg<T>)p.blo_l, (cg<T>)p.bhi_l};
+        cpa_body<T>(p, a, aa, tb, b);
+    }
+}
+
 // ---- k_mpc_step: the end of step t of a closed-loop simulation and the start of step t + 1,
 // one workgroup per instance, launched after every instance of the batch is done with step t.
 //   1. x = the slab's x0, u = the root's input of the final primal Z[(final_k + 1) % 3]; with
@@ -786,6 +1030,18 @@ const char* cpb_name(bool f32, bool lds_tabs) {
     if (f32) return lds_tabs ? "k_cpb<float, true>" : "k_cpb<float, false>";
     return lds_tabs ? "k_cpb<true>" : "k_cpb<false>";
 }
+
+CpaSlab cpa_layout(const Dev& p, int m) { return cpa_layout_dims(p.P, p.D, m); }
+
+hipError_t cpa_launch(const Dev& p, const CpbArg& a, const CpaArg& aa, hipStream_t stream) {
+    if (a.lds_tabs)
+        k_cpa<double, true><<<a.B, kCpbBlock, tab_elems(p) * sizeof(double), stream>>>(p, a, aa);
+    else
+        k_cpa<double, false><<<a.B, kCpbBlock, 0, stream>>>(p, a, aa);
+    return hipGetLastError();
+}
+
+const char* cpa_name(bool lds_tabs) { return lds_tabs ? "k_cpa<true>" : "k_cpa<false>"; }
 
 hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, bool f32, hipStream_t stream) {
     if (f32)

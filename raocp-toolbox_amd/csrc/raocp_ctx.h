@@ -216,6 +216,15 @@ struct raocp_ctx {
         int* done = nullptr;
         double* hist = nullptr;
         double* u0 = nullptr;
+        // the Anderson acceleration of raocp_cp_batch_run_aa (k_cpa): a second slab per instance
+        // and one log record per history row, sized for memory a_m and a_rows history rows
+        bool accel = false;          // the last batch call was accelerated
+        int a_m = 0;
+        size_t a_rows = 0;
+        size_t a_log_rows = 0;       // rows per instance the last accelerated batch's log is laid out by
+        raocp::CpaSlab alay{};
+        double* aslab = nullptr;
+        double* alog = nullptr;
         std::vector<int> fk;         // final_k per instance
         std::vector<double> hz, he, hu0;  // the sequential solves' final iterates and first inputs
         std::vector<double> hx0;     // ... and the state each instance's last solve was solved from

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "raocp_group_cp_run_warm",
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
     "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs", "raocp_cp_batch_mpc",
-    "raocp_evaluate", "raocp_cp_batch_evaluate",
+    "raocp_evaluate", "raocp_cp_batch_evaluate", "raocp_cp_batch_run_aa", "raocp_cp_batch_aa_log", "raocp_cp_batch_get_prev",
 ]
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -98,7 +98,11 @@ def load_library():
         "raocp_cp_run": (c_int, [vp, vp, c_int, c_double, c_double, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                  vp, vp]),
         "raocp_cp_batch_run": (c_int, [vp, c_int, vp, vp, vp, c_int, c_double, c_double, vp, vp, vp, vp]),
+        "raocp_cp_batch_run_aa": (c_int, [vp, c_int, vp, vp, vp, c_int, c_double, c_double, c_int, c_int, c_double,
+                                          c_double, vp, vp, vp, vp]),
+        "raocp_cp_batch_aa_log": (c_int, [vp, c_int, vp]),
         "raocp_cp_batch_get": (c_int, [vp, c_int, vp, vp]),
+        "raocp_cp_batch_get_prev": (c_int, [vp, c_int, vp, vp]),
         "raocp_cp_batch_first_inputs": (c_int, [vp, vp]),
         "raocp_cp_batch_mpc": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_double, c_double, c_int,
                                        vp, vp, vp, vp, vp, vp]),
@@ -344,10 +348,12 @@ class NativeContext:
         k = iters.value
         return status.value, err[:k].copy(), derr[:k].copy()
 
-    def cp_batch_run(self, x0, max_iters, tol, alpha, z0=None, eta0=None):
+    def cp_batch_run(self, x0, max_iters, tol, alpha, z0=None, eta0=None, accel=None):
         """B CP solves that share the problem and alpha: x0 is (B, nx); z0 (B, P) and eta0
         (B, D) are the starting iterates (both None: zeros). Returns (status[B] with 0 / 1 and
-        2 = NaN in a box, [error_cache], [delta_error_cache]), one (rows, 3) array per instance."""
+        2 = NaN in a box, [error_cache], [delta_error_cache]), one (rows, 3) array per instance.
+        accel = (m, every, reg, safeguard) runs the Anderson-accelerated kernel
+        (raocp_cp_batch_run_aa); cp_batch_accel_log(b) then returns instance b's log."""
         self._require_l()
         nx = self._packed.nx
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
@@ -367,10 +373,16 @@ class NativeContext:
         derr = np.zeros((max(B, 1), max(rows, 1), 3))
         status = np.zeros(max(B, 1), dtype=np.int32)
         iters = np.zeros(max(B, 1), dtype=np.int32)
-        self._check(self._lib.raocp_cp_batch_run(
-            self._h, B, _ptr(x0), None if z0 is None else _ptr(z0), None if eta0 is None else _ptr(eta0),
-            int(max_iters), float(tol), float(alpha), _ptr(status), _ptr(iters), _ptr(err), _ptr(derr)))
+        head = (self._h, B, _ptr(x0), None if z0 is None else _ptr(z0), None if eta0 is None else _ptr(eta0),
+                int(max_iters), float(tol), float(alpha))
+        tail = (_ptr(status), _ptr(iters), _ptr(err), _ptr(derr))
+        if accel is None:
+            self._check(self._lib.raocp_cp_batch_run(*head, *tail))
+        else:
+            m, every, reg, safeguard = accel
+            self._check(self._lib.raocp_cp_batch_run_aa(*head, int(m), int(every), float(reg), float(safeguard), *tail))
         self._batch_B = B
+        self._batch_iters = iters[:B].copy()
         return (status.astype(np.int64), [err[b, :iters[b]].copy() for b in range(B)],
                 [derr[b, :iters[b]].copy() for b in range(B)])
 
@@ -380,6 +392,22 @@ class NativeContext:
         z, e = np.empty(self.P, dtype=np.float64), np.empty(self.D, dtype=np.float64)
         self._check(self._lib.raocp_cp_batch_get(self._h, int(b), _ptr(z), _ptr(e)))
         return z, e
+
+    def cp_batch_get_prev(self, b):
+        """(z, eta) that instance b's last iteration was computed from (batches a kernel ran)."""
+        z, e = np.empty(self.P, dtype=np.float64), np.empty(self.D, dtype=np.float64)
+        self._check(self._lib.raocp_cp_batch_get_prev(self._h, int(b), _ptr(z), _ptr(e)))
+        return z, e
+
+    def cp_batch_accel_log(self, b):
+        """(iters[b], 12): the acceleration's log of instance b of the last accelerated batch, one
+        record per history row: code, j, prop, |r|_2, gamma[8] (include/raocp_hip.h)."""
+        B = getattr(self, "_batch_B", 0)
+        if not 0 <= int(b) < B:
+            raise IndexError(f"instance {b} of a batch of {B}")
+        out = np.zeros((max(int(self._batch_iters[int(b)]), 1), 12))
+        self._check(self._lib.raocp_cp_batch_aa_log(self._h, int(b), _ptr(out)))
+        return out[:int(self._batch_iters[int(b)])]
 
     def cp_batch_first_inputs(self):
         """(B, nu): the root's input of every instance's final primal."""

@@ -111,6 +111,7 @@ class Solver:
         self.batch_error_cache = []
         self.batch_delta_error_cache = []
         self.batch_simulation = None
+        self.batch_accel_log = []
 
     @property
     def cache(self):
@@ -196,7 +197,8 @@ class Solver:
         return status
 
     # ----- batched solves (extension): many initial states, one launch
-    def chock_batch(self, initial_states, max_iters=10, tol=1e-5, step_size=None, warm=False):
+    def chock_batch(self, initial_states, max_iters=10, tol=1e-5, step_size=None, warm=False,
+                    accel=0, accel_every=1, accel_reg=1e-10, accel_safeguard=1.0):
         """Chambolle-Pock for B initial states of the same problem at once (one workgroup per
         instance on the device). Returns an int array of chock's codes (0 converged, 1 not).
         warm=True continues every instance from the iterate the previous chock_batch left (the
@@ -205,11 +207,37 @@ class Solver:
         projection in some instances, the results are stored and ValueError names them.
         A float32 solver returns the same types, shapes and dtypes; it runs the batch kernel's
         float form when the environment has RAOCP_CPB_F32=1 and the solves one after another
-        otherwise (the same holds for simulate_batch)."""
+        otherwise (the same holds for simulate_batch).
+
+        accel=m (1 <= m <= 8) adds Anderson acceleration of memory m. With
+        v = (z, eta), g = T(v) one CP iteration and r = g - v, the last m differences of (g, r) are
+        kept; after iteration k with (k + 1) % accel_every == 0 the least-squares combination
+        gamma = (dR'dR + accel_reg (tr / j) I)^-1 dR'r is solved and g - dG gamma is proposed as
+        the next iterate. The iteration after it is a trial: kept if its ||r||_2 is at most
+        accel_safeguard times the one before the proposal, else the history is cleared and the
+        solve goes on from g. Every iteration, trials included, has its row in the error caches and
+        counts against max_iters; a rejected trial never ends the solve through tol.
+        batch_accel_log[b] is instance b's (iters, 12) log: code (0 plain, 1 proposal, 2 trial
+        accepted, 3 trial rejected, 4 solve refused), column count, what followed (0 nothing, 1 a
+        proposal, 2 a refused solve), ||r||_2, gamma[8]. accel=0 (the default) is the plain solve.
+        Out of scope: a float32 solver, a sharded context and a context the batch kernel does not
+        cover raise ValueError for accel > 0 (there is no sequential fallback); simulate_batch and
+        the single-solve chock are not accelerated; warm=True after an accelerated batch continues
+        from its iterate with an empty history."""
         nx = self.__raocp.state_dynamics_at_node(1).shape[1]
         x0 = normalise_initial_states(initial_states, nx)
         B = x0.shape[0]
         native = self.__cache.native
+        aa = None
+        if accel:
+            if not (isinstance(accel, (int, np.integer)) and 1 <= accel <= 8):
+                raise ValueError(f"accel must be 0 or in 1 .. 8, got {accel!r}")
+            if int(accel_every) < 1 or not accel_reg >= 0.0 or not accel_safeguard >= 0.0:
+                raise ValueError("accel_every must be >= 1, accel_reg and accel_safeguard >= 0")
+            if native.kernel_info(19) == "":
+                raise ValueError("accel > 0 needs the fp64 batch kernel: not available on a float32 solver, "
+                                 "a sharded context or a context the batch kernel does not cover")
+            aa = (int(accel), int(accel_every), float(accel_reg), float(accel_safeguard))
         z0 = e0 = None
         if warm:
             if B != self.__batch_size:
@@ -223,13 +251,14 @@ class Solver:
             self.__parameter_1 = self.__parameter_2 = float(step_size)
         print("timer started")
         tick = time.perf_counter()
-        status, errs, derrs = native.cp_batch_run(x0, int(max_iters), float(tol), self.__parameter_1, z0, e0)
+        status, errs, derrs = native.cp_batch_run(x0, int(max_iters), float(tol), self.__parameter_1, z0, e0, accel=aa)
         tock = time.perf_counter()
         print(f"timer stopped in {tock - tick:0.4f} seconds")
         self.__batch_size = B
         # the shape rules of error_cache: a single row is 1-D (solver.py:148-153)
         self.batch_error_cache = [e if e.shape[0] > 1 else e[0] for e in errs]
         self.batch_delta_error_cache = [e if e.shape[0] > 1 else e[0] for e in derrs]
+        self.batch_accel_log = [native.cp_batch_accel_log(b) for b in range(B)] if aa else []
         bad = [int(b) for b in np.flatnonzero(status == 2)]
         if bad:
             raise ValueError(f"Rectangle constraint - 'nan' value cannot be constrained (instances {bad})")
