@@ -139,6 +139,72 @@ struct Cp3Tasks {
     int lo[kCp3MaxR], hi[kCp3MaxR], t0[kCp3MaxR + 1];  // t0: first task of each range
 };
 
+// ---- host-built plans of the dynamics sweeps that the context (raocp_ctx.h) holds; the kernels
+// that read them are in raocp_dyn.hip, raocp_dynf.hip, raocp_dyn2.hip and raocp_dyn3.hip
+
+// row stride of a matrix table whose rows hold k (even) doubles: an odd number of 16-B
+// units, so the ds_read_b128 of lanes reading different rows spread over the banks
+constexpr __host__ __device__ int tstride(int k) { return (k / 2) % 2 == 0 ? k + 2 : k; }
+
+// raocp_dyn.hip: the subtree-blocked sweep
+constexpr int kMaxLevels = 31;    // tier depth limit (host plans within it)
+constexpr int kMaxTopStages = 62; // cut stage limit of k_dyn_top
+
+// level ranges of a tier's subtree: from the kernel argument when the tier is regular
+// (every subtree the same shape, ids consecutive), else from the host table
+struct TierArg {
+    int regular;
+    int boff;  // first subtree of this launch (a shard launches only the subtrees it owns)
+    int lo0[kMaxLevels + 1];
+    int cnt[kMaxLevels + 1];
+    int pl0[kMaxLevels + 1];  // first (kind, class) pair of the parents of level l (absolute)
+};
+
+// raocp_dynf.hip: the split sweep k_dyn_up / k_dyn_down
+constexpr int kFuseTiers = 4;
+
+struct FuseTier {
+    int s0, s1;        // roots at stage s0, levels s0 .. s1-1, boundary nodes at s1
+    int r;             // subtrees of this tier under one subtree of the tier above (or the top)
+    int c0, c1, p0, p1;
+    int maxch;         // widest child level of one subtree (P rows)
+    int fm;            // F rows in the forward sweep: 1 every pair of the tier, 2 per level
+    int fold;          // one-phase backward levels (per-pair WT tables, back_fold)
+    int nnl;           // nonleaf nodes of one subtree (levels 0 .. L-1)
+    int ngroups;       // subtrees of the tier above (tickets / flags)
+    TierArg ta;        // regular tier: level sizes and first nodes
+    unsigned* cnt;     // [ngroups] tickets
+    unsigned* flag;    // [ngroups] forward released by the tier above
+};
+
+struct FuseArg {
+    int K;                          // tiers below the top
+    FuseTier t[kFuseTiers];
+    int s, T, nb, c1, p1, maxch_top; // the top: stages [0, s), nodes [0, T), nb boundary roots
+    int fold_top;                   // the top's backward levels in one phase
+    unsigned* epoch;
+    int* err;                       // set to 1 by a workgroup whose wait timed out
+    long long timeout;              // per wait, 100 MHz ticks
+    ChkArg ck;                      // the previous CP iteration's stopping test
+};
+
+// raocp_dyn2.hip: a tile of the per-stage MFMA dynamics
+struct DynTile {
+    int first;  // offset into the launch's node list
+    int cnt;    // nodes (<= 16)
+    int tab;    // weight table
+    int pad;
+};
+
+// raocp_dyn3.hip: one stage of the sweep (host-built)
+struct Dy3Stage {
+    int i0, i1;   // parents of the stage
+    int leaf;     // the children are leaves (stage N - 1)
+    int cls;      // offline class of the stage's parents
+    int kind[4];  // child kind (A, B pair) of slot k
+    int pair[4];  // (kind, class) pair of slot k
+};
+
 // agent-scope relaxed accesses (global_store / global_load ... sc1): write-through stores and
 // L1-bypassing loads for values another workgroup of the same launch reads (MI355X: per-XCD
 // L2s are not coherent with each other)

@@ -52,7 +52,7 @@ template <class T>
 using lds = __attribute__((address_space(3))) T;
 
 constexpr __host__ __device__ int rup_(int a, int b) { return (a + b - 1) / b * b; }
-// the row strides of the dynamics tables (raocp_dyn.hip tstride)
+// the row strides of the dynamics tables (raocp_common.h tstride)
 constexpr __host__ __device__ int tstride_(int k) { return (k / 2) % 2 == 0 ? k + 2 : k; }
 
 __device__ __forceinline__ int e3(const Dev& p, int j) { return p.E3 + 1 + (j - 1) * p.nx; }

@@ -1,21 +1,32 @@
 // raocp_ctx.h -- the context behind the C-ABI (include/raocp_hip.h): struct raocp_ctx with its
 // allocation / upload helpers, the error helpers (fail, HIPCHK) and the environment-switch
-// readers. Included by raocp_capi.hip only, after the kernel headers.
+// readers. Self-contained (it names only types of raocp_common.h and of the launch headers), so
+// any host unit of the library may include it: raocp_capi.hip and raocp_batch.hip do, through
+// raocp_host.h. The helpers are inline and the error string is one inline variable: whichever
+// unit fails, raocp_last_error() returns its message.
 #pragma once
 
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "raocp_common.h"
+#include "raocp_dynr.h"
+#include "raocp_cpb.h"
+#include "raocp_eval.h"
 #include "raocp_path.h"
+#include "../../include/raocp_hip.h"
 
-using raocp::Ctl;
-using raocp::CpPath;
-using raocp::DynPath;
-using raocp::Dev;
-using raocp::kBlock;
+namespace raocp {
 
-namespace {
+inline thread_local std::string g_err;
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
+inline int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
@@ -27,12 +38,20 @@ int fail(int code, const std::string& msg) {
             return fail(RAOCP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
     } while (0)
 
-int cdiv(int a, int b) { return b <= 0 ? 0 : (a + b - 1) / b; }
+inline int cdiv(int a, int b) { return b <= 0 ? 0 : (a + b - 1) / b; }
 
 // CP iterations per captured graph: a multiple of 6 (buffer rotation period, see rotated())
 constexpr int kGraphBatch = 24;
 
-}  // namespace
+}  // namespace raocp
+
+using raocp::Ctl;
+using raocp::CpPath;
+using raocp::DynPath;
+using raocp::Dev;
+using raocp::cdiv;
+using raocp::fail;
+using raocp::kGraphBatch;
 
 struct raocp_ctx {
     int device = 0;
@@ -270,19 +289,23 @@ struct raocp_ctx {
     }
 };
 
-namespace {
+namespace raocp {
 
 // environment switches: each caller keeps its own default and combination rule
-bool env_flag(const char* name, bool dflt) {
+inline bool env_flag(const char* name, bool dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) != 0 : dflt;
 }
-int env_int(const char* name, int dflt) {
+inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
 // RAOCP_FUSE_TIMEOUT_MS: how long a hand-off wait of the co-resident sweeps may last, in
 // 100 MHz ticks (1000 ms by default: a wait normally lasts microseconds)
-long long fuse_timeout_ticks() { return std::max(1, env_int("RAOCP_FUSE_TIMEOUT_MS", 1000)) * 100000LL; }
+inline long long fuse_timeout_ticks() { return std::max(1, env_int("RAOCP_FUSE_TIMEOUT_MS", 1000)) * 100000LL; }
 
-}  // namespace
+}  // namespace raocp
+
+using raocp::env_flag;
+using raocp::env_int;
+using raocp::fuse_timeout_ticks;

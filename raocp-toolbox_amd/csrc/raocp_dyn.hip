@@ -47,9 +47,7 @@ __device__ __forceinline__ d2v ld2(const ldsd* p) { return *(const lds2*)p; }
 __device__ __forceinline__ d2v ld2(const glbd* p) { return *(const glb2*)p; }
 
 constexpr __host__ __device__ int rup(int a, int b) { return (a + b - 1) / b * b; }
-// row stride of a matrix table whose rows hold k (even) doubles: an odd number of 16-B
-// units, so the ds_read_b128 of lanes reading different rows spread over the banks
-constexpr __host__ __device__ int tstride(int k) { return (k / 2) % 2 == 0 ? k + 2 : k; }
+// (tstride, the row stride of a matrix table: raocp_common.h)
 
 template <int NXc, int NUc>
 struct Geo {
@@ -493,8 +491,7 @@ __global__ void __launch_bounds__(kDynBlock) k_dyn_stage_f(Dev p, Bufs bf, const
 }
 
 // ---- subtree-blocked sweep ------------------------------------------------------------
-constexpr int kMaxLevels = 31;    // tier depth limit (host plans within it)
-constexpr int kMaxTopStages = 62; // cut stage limit of k_dyn_top
+// (kMaxLevels, kMaxTopStages and TierArg: raocp_common.h)
 
 struct Prologue {
     int lo[kMaxLevels + 1], hi[kMaxLevels + 1], off[kMaxLevels + 1];
@@ -586,16 +583,6 @@ __device__ __forceinline__ void rows_in_r(bool dmaok, ldsd* dst, int w, const do
     }, rot < 0 ? 0 : rot);
     if (rot >= 0) rot += g;
 }
-
-// level ranges of a tier's subtree: from the kernel argument when the tier is regular
-// (every subtree the same shape, ids consecutive), else from the host table
-struct TierArg {
-    int regular;
-    int boff;  // first subtree of this launch (a shard launches only the subtrees it owns)
-    int lo0[kMaxLevels + 1];
-    int cnt[kMaxLevels + 1];
-    int pl0[kMaxLevels + 1];  // first (kind, class) pair of the parents of level l (absolute)
-};
 
 // level l's node range {lo, hi, off} of this workgroup's subtree: computed from the kernel
 // argument when the tier is regular (wave-uniform arithmetic, no LDS round trip and no

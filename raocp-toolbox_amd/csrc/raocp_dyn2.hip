@@ -15,12 +15,7 @@
 // nodes of a stage grouped by child kind / class / (kind, class) pair); one wave per tile,
 // A operands loaded straight from global (a node's row is contiguous), no LDS.
 
-struct DynTile {
-    int first;  // offset into the launch's node list
-    int cnt;    // nodes (<= 16)
-    int tab;    // weight table
-    int pad;
-};
+// (DynTile, a tile of a launch: raocp_common.h)
 
 // lane l: its tile's node for A row lo (or -1)
 __device__ __forceinline__ int tile_node(const DynTile& t, const int* __restrict__ idx, int lo) {

@@ -59,14 +59,7 @@ __device__ __forceinline__ void mmts(const WLs<T, R, K>& W, const T (&b)[(K + 15
             acc[ro] = MF<T>::mma(W.get(ro, s), b[s >> 2][s & 3], acc[ro]);
 }
 
-// one stage of the sweep (host-built)
-struct Dy3Stage {
-    int i0, i1;   // parents of the stage
-    int leaf;     // the children are leaves (stage N - 1)
-    int cls;      // offline class of the stage's parents
-    int kind[4];  // child kind (A, B pair) of slot k
-    int pair[4];  // (kind, class) pair of slot k
-};
+// (Dy3Stage, one stage of the sweep: raocp_common.h)
 
 template <class T, int NX, int NU>
 struct Dy3Lds {

@@ -19,35 +19,10 @@
 // every wait is bounded (FuseArg::timeout) and a timed-out workgroup sets the error word,
 // which every workgroup of a later launch reads at its start and then leaves at once.
 
-constexpr int kFuseTiers = 4;
+// (kFuseTiers, FuseTier and FuseArg: raocp_common.h)
 // workgroup size of the fused sweep: at most 512 lanes leaves 256 VGPRs per lane (the tier,
 // top and forward routines inlined into one kernel spill at 1024 lanes' 128)
 constexpr int kFuseBlock = 512;
-
-struct FuseTier {
-    int s0, s1;        // roots at stage s0, levels s0 .. s1-1, boundary nodes at s1
-    int r;             // subtrees of this tier under one subtree of the tier above (or the top)
-    int c0, c1, p0, p1;
-    int maxch;         // widest child level of one subtree (P rows)
-    int fm;            // F rows in the forward sweep: 1 every pair of the tier, 2 per level
-    int fold;          // one-phase backward levels (per-pair WT tables, back_fold)
-    int nnl;           // nonleaf nodes of one subtree (levels 0 .. L-1)
-    int ngroups;       // subtrees of the tier above (tickets / flags)
-    TierArg ta;        // regular tier: level sizes and first nodes
-    unsigned* cnt;     // [ngroups] tickets
-    unsigned* flag;    // [ngroups] forward released by the tier above
-};
-
-struct FuseArg {
-    int K;                          // tiers below the top
-    FuseTier t[kFuseTiers];
-    int s, T, nb, c1, p1, maxch_top; // the top: stages [0, s), nodes [0, T), nb boundary roots
-    int fold_top;                   // the top's backward levels in one phase
-    unsigned* epoch;
-    int* err;                       // set to 1 by a workgroup whose wait timed out
-    long long timeout;              // per wait, 100 MHz ticks
-    ChkArg ck;                      // the previous CP iteration's stopping test
-};
 
 // diagnostics: thread 0 stamps the next slot of this workgroup's path (p.stamps != nullptr)
 __device__ __forceinline__ void fz_stamp(const Dev& p, Prologue& pl) {

@@ -35,7 +35,7 @@ struct TierSizes {
     int KP, KF, NUP, PS;
     int SKP, SKF, SNU;
 };
-// limits of the kernels' argument structs (raocp_dyn.hip kMaxLevels, kMaxTopStages)
+// limits of the kernels' argument structs (raocp_common.h kMaxLevels, kMaxTopStages)
 struct TierLimits {
     int max_levels, max_top_stages;
 };

@@ -112,6 +112,26 @@ static void cpu_checks() {
     float ms = 0;
     CHECK(raocp_cp_bench(nullptr, nullptr, 1, 0.1, &ms) != RAOCP_OK);
     raocp_ctx_destroy(nullptr);
+    // the batch, MPC and evaluation entry points are another translation unit (raocp_batch.hip)
+    // than raocp_last_error: one error string serves both, whichever unit failed last
+    auto null_arg = [](int rc) { return rc == RAOCP_ERR_ARG && strcmp(raocp_last_error(), "null argument") == 0; };
+    int ist = 0;
+    double d = 0;
+    CHECK(null_arg(raocp_cp_batch_run(nullptr, 1, &d, nullptr, nullptr, 1, 0.0, 0.1, &ist, &ist, &d, &d)));
+    CHECK(null_arg(raocp_cp_batch_run_aa(nullptr, 1, &d, nullptr, nullptr, 1, 0.0, 0.1, 2, 1, 0.0, 1.0, &ist, &ist, &d, &d)));
+    CHECK(null_arg(raocp_cp_batch_mpc(nullptr, 1, 1, &d, &ist, 1, 0.0, 0.1, 0, &d, &d, &d, &ist, &ist, &d)));
+    CHECK(null_arg(raocp_evaluate(nullptr, nullptr, 0, &d, nullptr)));
+    CHECK(null_arg(raocp_cp_batch_evaluate(nullptr, &d)));
+    CHECK(null_arg(raocp_cp_batch_get(nullptr, 0, &d, &d)));
+    CHECK(null_arg(raocp_cp_batch_first_inputs(nullptr, &d)));
+    {
+        Problem b(4, 4, 2);
+        b.stage[5] = 1;  // raocp_capi.hip's validation fails with a message of its own
+        b.t.stage = b.stage.data();
+        CHECK(raocp_ctx_create(&b.t, &b.p, 0, &c) == RAOCP_ERR_TREE);
+        CHECK(strcmp(raocp_last_error(), "stage must be non-decreasing in node id") == 0);
+    }
+    CHECK(null_arg(raocp_cp_batch_get(nullptr, 0, &d, &d)));
 }
 
 static void gpu_checks() {

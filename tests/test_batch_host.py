@@ -38,9 +38,11 @@ def test_header_declares_batch_entry_points():
 
 
 def test_batch_kernel_unit_is_in_the_build_and_compiles(tmp_path):
-    mk = open(os.path.join(PKG, "Makefile")).read()
-    assert "$(OBJ)/raocp_cpb.o" in mk.split("OBJS :=")[1].split("\n")[0]
-    assert "csrc/raocp_cpb.hip" in mk
+    # what `make all` would run from scratch: the unit is compiled and its object is linked
+    cmds = subprocess.run(["make", "-C", PKG, "-n", "-B", "all"], capture_output=True, text=True, check=True).stdout
+    link = [line for line in cmds.splitlines() if " -shared " in line]
+    assert len(link) == 1 and "/raocp_cpb.o" in link[0].split(" -o ")[0], link
+    assert any(" -c csrc/raocp_cpb.hip " in line for line in cmds.splitlines())
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.fail("hipcc not found: the batch kernel cannot be built")

@@ -11,6 +11,8 @@ No compute call touches a GPU here.
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -43,6 +45,20 @@ def test_library_exports_every_declared_symbol():
     # the error channel works without a device
     _native.load_library()
     assert isinstance(_native.load_library().raocp_last_error(), (bytes, type(None)))
+
+
+def test_shared_host_state_is_one_object_in_the_library():
+    """The error string and the per-device sweep locks are shared by the library's host units
+    (raocp_capi.hip, raocp_batch.hip): each is one symbol, not one per unit."""
+    if not os.path.exists(_native.LIB_PATH) or not shutil.which("nm"):
+        pytest.skip("libraocp_hip.so not built (run __graft_entry__.build()), or no nm")
+    out = subprocess.run(["nm", "-C", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    # "<address> <type> <demangled name>", the name with or without an ABI tag ("g_err[abi:cxx11]");
+    # "... for <name>" are a variable's guard and TLS helpers
+    names = [f[2].split("[")[0] for f in (line.split(None, 2) for line in out.splitlines())
+             if len(f) == 3 and " for " not in f[2]]
+    for var in ("g_err", "g_sweep_mu"):
+        assert [n for n in names if n.split("::")[-1] == var] == ["raocp::" + var], var
 
 
 def test_missing_extension_fails_loudly(monkeypatch):

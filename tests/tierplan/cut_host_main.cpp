@@ -33,7 +33,7 @@ int main() {
     const int KP = rup(nx, 8), KF = rup(nx + nu, 8), NUP = rup(nu, 2), PS = NUP + rup(nx, 2);
     const raocp::TierSizes z{nx, nu, KP, KF, NUP, PS, tstride(KP), tstride(KF), tstride(NUP)};
     const raocp::TierTree tr{n, N, stage_ptr.data(), ch_start.data(), nch.data(), cls_ptr.data(), pair_ptr.data(), nkind};
-    // the argument structs' limits in raocp_dyn.hip (kMaxLevels, kMaxTopStages), as plan_host_main.cpp
+    // the argument structs' limits in raocp_common.h (kMaxLevels, kMaxTopStages), as plan_host_main.cpp
     const raocp::TierPlanResult res = raocp::plan_tiers(tr, z, raocp::TierLimits{31, 62}, n_cus, true, false);
     printf("cut %d\n", res.cut);
     for (const auto& t : res.tiers) printf("tier %d %d\n", t.s0, t.s1);

@@ -79,7 +79,7 @@ bool run(const Case& cs) {
         pair_ptr[s] = C * s;  // one pair per child slot of each class
     }
     const raocp::TierTree tr{n, N, stage_ptr.data(), ch_start.data(), nch.data(), cls_ptr.data(), pair_ptr.data(), C};
-    // the argument structs' limits in raocp_dyn.hip (kMaxLevels, kMaxTopStages); no tree here comes near them
+    // the argument structs' limits in raocp_common.h (kMaxLevels, kMaxTopStages); no tree here comes near them
     const raocp::TierLimits lim{31, 62};
     const raocp::TierPlanResult got = raocp::plan_tiers(tr, cs.z, lim, 256, cs.fold_ok, cs.per_stage);
     const bool ok = same(got, cs.want);
