@@ -155,6 +155,8 @@ int raocp_reset_iterate(raocp_ctx* ctx);
  * ran; before any: by how one would run now, as op 13 reports it); op 19: the kernel of
  * raocp_cp_batch_run_aa, "k_cpa<true>" / "k_cpa<false>" (the shared tables staged in LDS or
  * not), or "" on a context that call refuses (fp32, sharded, or one k_cpb does not cover);
+ * op 20: the step kernel of raocp_cp_batch_mpc_aa, "k_mpc_step_aa", or "" on a context that call
+ * refuses (the contexts of op 19);
  * written NUL-terminated to buf. */
 int raocp_kernel_info(raocp_ctx* ctx, int op, char* buf, int cap);
 
@@ -239,7 +241,8 @@ int raocp_cp_batch_run(raocp_ctx* ctx, int B, const double* x0 /*[B][nx]*/,
 int raocp_cp_batch_run_aa(raocp_ctx* ctx, int B, const double* x0, const double* z0, const double* eta0,
                           int max_iters, double tol, double alpha, int accel, int accel_every, double accel_reg,
                           double accel_safeguard, int* status, int* iters, double* err_hist, double* delta_hist);
-/* The acceleration's log of instance b of the last raocp_cp_batch_run_aa: iters[b] records of 12
+/* The acceleration's log of instance b of the last raocp_cp_batch_run_aa (or of instance b's last
+ * solve of the last raocp_cp_batch_mpc_aa, iters[b] then being that solve's): iters[b] records of 12
  * doubles, one per history row: code (0 plain, 1 proposal made, 2 trial accepted, 3 trial
  * rejected, 4 solve refused), j (columns when the solve ran, else after the push), prop (what
  * followed in this iteration: 0 nothing, 1 a proposal, 2 a refused solve; it tells what an
@@ -284,6 +287,27 @@ int raocp_cp_batch_mpc(raocp_ctx* ctx, int B, int T, const double* x0 /*[B][nx]*
                        int max_iters, double tol, double alpha, int warm,
                        double* X /*[B][T+1][nx]*/, double* U /*[B][T][nu]*/, double* cost /*[B][T]*/,
                        int* status /*[B][T]*/, int* iters /*[B][T]*/, double* err /*[B][T][3]*/);
+/* raocp_cp_batch_mpc with every step of every instance solved by raocp_cp_batch_run_aa's kernel
+ * (k_cpa; accel = m in 1 .. 8 and accel_every, accel_reg, accel_safeguard as there). Every step
+ * starts with an empty acceleration history (no columns, no previous pair, no pending trial)
+ * whatever warm is: a new x0 is a new fixed-point map; warm != 0 still carries the iterate over.
+ * One launch per step (k_mpc_step_aa) does what k_mpc_step does, reduces the log of the solve that
+ * has just ended to aa_counts[b][t][0..3] = proposals made, trials accepted, trials rejected,
+ * solves refused (log records with prop == 1, code == 2, code == 3, prop == 2) and clears the
+ * instance's acceleration state for the next step; no log is downloaded inside the loop. The
+ * counts of a step a frozen instance did not solve are zero; the step that froze it has the
+ * counts of that solve. The other outputs, the freezing rule and the follow-up calls are those of
+ * raocp_cp_batch_mpc; raocp_cp_batch_aa_log then serves every instance's last solve. Errors: those
+ * of raocp_cp_batch_mpc (aa_counts NULL included), then those of raocp_cp_batch_run_aa:
+ * RAOCP_ERR_ARG for accel outside 1 .. 8, accel_every < 1 or a negative accel_reg /
+ * accel_safeguard, RAOCP_ERR_STATE on an fp32 context or one k_cpb does not cover (there is no
+ * sequential form and no fp32 form). kernel_info op 20 names the step kernel. */
+int raocp_cp_batch_mpc_aa(raocp_ctx* ctx, int B, int T, const double* x0 /*[B][nx]*/, const int* scen /*[B][T]*/,
+                          int max_iters, double tol, double alpha, int warm, int accel, int accel_every,
+                          double accel_reg, double accel_safeguard,
+                          double* X /*[B][T+1][nx]*/, double* U /*[B][T][nu]*/, double* cost /*[B][T]*/,
+                          int* status /*[B][T]*/, int* iters /*[B][T]*/, double* err /*[B][T][3]*/,
+                          int* aa_counts /*[B][T][4]*/);
 
 /* Evaluate a primal: the risk-averse cost of its policy and how far it is from feasible
  * (raocp_eval.hip). With l_j = |sqrtQ_j x_anc(j)|^2 + |sqrtR_j u_anc(j)|^2 the stage cost of

@@ -1,7 +1,8 @@
 // raocp_aa_ops.h — the small solver of the Anderson-accelerated batch kernel (k_cpa,
 // raocp_cpb.hip) that a host program can run too: the regularised Cholesky solve of the
-// least-squares normal equations. No HIP runtime dependency: a plain host compiler takes this
-// file (tests/accel/aa_host_main.cpp).
+// least-squares normal equations, and the classification of one log record into the counters the
+// accelerated step kernel keeps. No HIP runtime dependency: a plain host compiler takes this
+// file (tests/accel/aa_host_main.cpp, tests/accel/aa_count_main.cpp).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -14,6 +15,18 @@ namespace raocp {
 
 constexpr int kAaMaxM = 8;   // the largest memory (columns) of the acceleration
 constexpr int kAaRec = 12;   // doubles of one log record: code, j, prop, |r|_2, gamma[8]
+
+// What one log record adds to the four counters of a solve (k_mpc_step_aa, aa_counts of
+// raocp_cp_batch_mpc_aa): cnt[0] proposals made (prop == 1), cnt[1] trials accepted (code == 2),
+// cnt[2] trials rejected (code == 3), cnt[3] solves refused (prop == 2). A record may add to two of
+// them: an accepted trial that goes on to propose or to a refused solve.
+constexpr int kAaCounts = 4;
+RAOCP_AA_HD void aa_count(int code, int prop, int* cnt) {
+    cnt[0] += prop == 1 ? 1 : 0;
+    cnt[1] += code == 2 ? 1 : 0;
+    cnt[2] += code == 3 ? 1 : 0;
+    cnt[3] += prop == 2 ? 1 : 0;
+}
 
 // gamma = (G + reg (tr G / j) I)^-1 b for the j <= kAaMaxM leading rows and columns of the
 // symmetric G (row stride kAaMaxM; the lower triangle is read), by Cholesky, all in double.

@@ -1,5 +1,5 @@
 // raocp_batch.hip — the host code of the batched solves (raocp_cp_batch_*), the closed-loop
-// simulation of a batch (raocp_cp_batch_mpc) and the evaluation of a primal (raocp_evaluate,
+// simulation of a batch (raocp_cp_batch_mpc, raocp_cp_batch_mpc_aa) and the evaluation of a primal (raocp_evaluate,
 // raocp_cp_batch_evaluate). Host code only: it launches through raocp_cpb.h and raocp_eval.h
 // (the kernels are in raocp_cpb.hip and raocp_eval.hip) and falls back on the public single-solve
 // entry points of raocp_capi.hip, so it compiles without the kernel families of that unit.
@@ -262,6 +262,33 @@ int batch_ensure_aa(raocp_ctx* c, int B, int m) {
     return RAOCP_OK;
 }
 
+// k_cpa's arguments over the buffers batch_ensure_aa has sized
+raocp::CpaArg batch_aa_arg(raocp_ctx* c, const AaOpt& aa) {
+    raocp::CpaArg ca{};
+    ca.slab = c->bt.aslab;
+    ca.lay = c->bt.alay;
+    ca.log = c->bt.alog;
+    ca.every = aa.every;
+    ca.reg = aa.reg;
+    ca.safeguard = aa.safeguard;
+    return ca;
+}
+
+// the checks of an accelerated call, in the order raocp_cp_batch_run_aa has always made them: the
+// options (RAOCP_ERR_ARG) ...
+int aa_check_opt(const AaOpt& aa) {
+    if (aa.m < 1 || aa.m > raocp::kAaMaxM) return fail(RAOCP_ERR_ARG, "accel must be in 1 .. 8");
+    if (aa.every < 1) return fail(RAOCP_ERR_ARG, "accel_every must be >= 1");
+    if (!(aa.reg >= 0.0) || !(aa.safeguard >= 0.0)) return fail(RAOCP_ERR_ARG, "accel_reg and accel_safeguard must be >= 0");
+    return RAOCP_OK;
+}
+// ... and, after the sharded-context check of the plain call, the context (RAOCP_ERR_STATE)
+int aa_check_ctx(const raocp_ctx* c) {
+    if (c->f32) return fail(RAOCP_ERR_STATE, "accelerated batched solves are not available on an fp32 context");
+    if (!cpb_on(c)) return fail(RAOCP_ERR_STATE, "accelerated batched solves need the batch kernel, which does not cover this context");
+    return RAOCP_OK;
+}
+
 // aa: nullptr runs k_cpb; else k_cpa with these options
 int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, const double* eta0, int max_iters,
                      double tol, double alpha, int* status, int* iters, double* err_hist, double* delta_hist,
@@ -274,15 +301,7 @@ int batch_run_kernel(raocp_ctx* c, int B, const double* x0, const double* z0, co
     if ((rc = batch_start(c, B, rows, x0, z0, eta0, max_iters, tol, alpha, hc))) return rc;
     if (aa && (rc = batch_ensure_aa(c, B, aa->m))) return rc;
     const raocp::CpbArg a = batch_arg(c, B, rows);
-    raocp::CpaArg ca{};
-    if (aa) {
-        ca.slab = bt.aslab;
-        ca.lay = bt.alay;
-        ca.log = bt.alog;
-        ca.every = aa->every;
-        ca.reg = aa->reg;
-        ca.safeguard = aa->safeguard;
-    }
+    const raocp::CpaArg ca = aa ? batch_aa_arg(c, *aa) : raocp::CpaArg{};
     rc = batch_solve(c, a, rows, [&]() -> int {
         HIPCHK(aa ? raocp::cpa_launch(c->dev, a, ca, c->stream) : raocp::cpb_launch(c->dev, a, c->f32, c->stream));
         return RAOCP_OK;
@@ -375,16 +394,10 @@ int batch_run(raocp_ctx* c, int B, const double* x0, const double* z0, const dou
     if (B < 1 || B > 4096) return fail(RAOCP_ERR_ARG, "batch size must be in 1 .. 4096");
     if ((z0 == nullptr) != (eta0 == nullptr)) return fail(RAOCP_ERR_ARG, "z0 and eta0 are given together");
     if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
-    if (aa) {
-        if (aa->m < 1 || aa->m > raocp::kAaMaxM) return fail(RAOCP_ERR_ARG, "accel must be in 1 .. 8");
-        if (aa->every < 1) return fail(RAOCP_ERR_ARG, "accel_every must be >= 1");
-        if (!(aa->reg >= 0.0) || !(aa->safeguard >= 0.0)) return fail(RAOCP_ERR_ARG, "accel_reg and accel_safeguard must be >= 0");
-    }
+    int rc;
+    if (aa && (rc = aa_check_opt(*aa))) return rc;
     if (c->comm || c->sh_R != 1) return fail(RAOCP_ERR_STATE, "batched solves are not available on a sharded context");
-    if (aa) {
-        if (c->f32) return fail(RAOCP_ERR_STATE, "accelerated batched solves are not available on an fp32 context");
-        if (!cpb_on(c)) return fail(RAOCP_ERR_STATE, "accelerated batched solves need the batch kernel, which does not cover this context");
-    }
+    if (aa && (rc = aa_check_ctx(c))) return rc;
     c->bt.B = 0;
     c->bt.accel = false;
     if (aa || cpb_on(c)) return batch_run_kernel(c, B, x0, z0, eta0, max_iters, tol, alpha, status, iters, err_hist, delta_hist, aa);
@@ -414,11 +427,11 @@ int batch_get(raocp_ctx* c, int b, double* z, double* eta, bool prev) {
     return copy_out(c, eta, (const double*)(slab + (size_t)bt.lay.e[k % 2] * w), (size_t)c->D, 0);
 }
 
-// ---- closed-loop simulation of a batch (raocp_cp_batch_mpc)
+// ---- closed-loop simulation of a batch (raocp_cp_batch_mpc, raocp_cp_batch_mpc_aa)
 
 // the per-step records on the device, as k_mpc_step takes them: one block, every array on a
-// 256-B boundary
-int mpc_ensure(raocp_ctx* c, int B, int T, raocp::MpcArg* mb) {
+// 256-B boundary; counts (an accelerated simulation only): [B][T][kAaCounts] ints behind them
+int mpc_ensure(raocp_ctx* c, int B, int T, raocp::MpcArg* mb, int** counts) {
     size_t at = 0;
     auto take = [&](size_t bytes) {
         const size_t o = at;
@@ -430,6 +443,7 @@ int mpc_ensure(raocp_ctx* c, int B, int T, raocp::MpcArg* mb) {
     const size_t o_X = take((size_t)B * (T + 1) * c->nx * sizeof(double)), o_U = take(BT * c->nu * sizeof(double));
     const size_t o_cost = take(BT * sizeof(double)), o_status = take(BT * sizeof(int)), o_iters = take(BT * sizeof(int));
     const size_t o_err = take(BT * 3 * sizeof(double));
+    const size_t o_cnt = counts ? take(BT * raocp::kAaCounts * sizeof(int)) : 0;
     if (at > c->mpc_cap) {
         mpc_free(c);
         HIPCHK(hipMalloc(&c->mpc_buf, at));
@@ -444,6 +458,7 @@ int mpc_ensure(raocp_ctx* c, int B, int T, raocp::MpcArg* mb) {
     mb->status = (int*)(base + o_status);
     mb->iters = (int*)(base + o_iters);
     mb->err = (double*)(base + o_err);
+    if (counts) *counts = (int*)(base + o_cnt);
     return RAOCP_OK;
 }
 
@@ -460,9 +475,13 @@ void mpc_final_k(std::vector<int>& fk, int B, int T, const int* iters) {
 }
 
 // the loop on the device: per step the chunked k_cpb launches with their done poll, then one
-// k_mpc_step launch; nothing else crosses the host boundary inside the T loop
+// k_mpc_step launch; nothing else crosses the host boundary inside the T loop. aa: nullptr runs
+// k_cpb and k_mpc_step; else k_cpa with these options and k_mpc_step_aa, which fills aa_counts and
+// empties the acceleration's state on the device (the slabs and the log are sized and cleared
+// once, before the loop)
 int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
-                     double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+                     double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err,
+                     const AaOpt* aa, int* aa_counts) {
     auto& bt = c->bt;
     const size_t rows = (size_t)max_iters + 1, BT = (size_t)B * T;
     int rc;
@@ -470,23 +489,27 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
     if (!c->d_mpc_ab && (rc = upload_t(c, &c->d_mpc_ab, c->h_mpc_ab))) return rc;
     std::vector<Ctl> hc;
     if ((rc = batch_start(c, B, rows, x0, nullptr, nullptr, max_iters, tol, alpha, hc))) return rc;
+    if (aa && (rc = batch_ensure_aa(c, B, aa->m))) return rc;
     raocp::MpcArg m{};
-    if ((rc = mpc_ensure(c, B, T, &m))) return rc;
+    int* d_counts = nullptr;
+    if ((rc = mpc_ensure(c, B, T, &m, aa ? &d_counts : nullptr))) return rc;
     HIPCHK(hipMemsetAsync(m.frz, 0xff, (size_t)B * sizeof(int), c->stream));  // -1: running
     HIPCHK(hipMemcpyAsync((void*)m.scen, scen, BT * sizeof(int), hipMemcpyHostToDevice, c->stream));
     const raocp::CpbArg a = batch_arg(c, B, rows);
+    const raocp::CpaArg ca = aa ? batch_aa_arg(c, *aa) : raocp::CpaArg{};
     m.ab = c->d_mpc_ab;
     m.T = T;
     m.warm = warm ? 1 : 0;
     for (int t = 0; t < T; ++t) {
         rc = batch_solve(c, a, rows, [&]() -> int {
-            HIPCHK(raocp::cpb_launch(c->dev, a, c->f32, c->stream));
+            HIPCHK(aa ? raocp::cpa_launch(c->dev, a, ca, c->stream) : raocp::cpb_launch(c->dev, a, c->f32, c->stream));
             return RAOCP_OK;
         });
         if (rc) return rc;
         m.t = t;
         m.last = t == T - 1 ? 1 : 0;
-        HIPCHK(raocp::mpc_step_launch(c->dev, a, m, c->f32, c->stream));
+        HIPCHK(aa ? raocp::mpc_step_aa_launch(c->dev, a, m, ca, d_counts, c->stream)
+                  : raocp::mpc_step_launch(c->dev, a, m, c->f32, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(X, m.X, (size_t)B * (T + 1) * c->nx * sizeof(double), hipMemcpyDeviceToHost));
@@ -495,9 +518,12 @@ int batch_mpc_kernel(raocp_ctx* c, int B, int T, const double* x0, const int* sc
     HIPCHK(hipMemcpy(status, m.status, BT * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(iters, m.iters, BT * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(err, m.err, BT * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (aa) HIPCHK(hipMemcpy(aa_counts, d_counts, BT * raocp::kAaCounts * sizeof(int), hipMemcpyDeviceToHost));
     mpc_final_k(bt.fk, B, T, iters);
     bt.B = B;
     bt.kernel = true;
+    bt.accel = aa != nullptr;  // raocp_cp_batch_aa_log: the log holds every instance's last solve
+    bt.a_log_rows = rows;
     return RAOCP_OK;
 }
 
@@ -673,10 +699,18 @@ int raocp_cp_batch_first_inputs(raocp_ctx* c, double* u0) {
     return RAOCP_OK;
 }
 
-int raocp_cp_batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
-                       double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+}  // extern "C"
+
+namespace {
+
+// raocp_cp_batch_mpc (aa == nullptr) and raocp_cp_batch_mpc_aa: the checks of the plain call in the
+// order it has always made them, then those of an accelerated call, then the loop
+int batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol, double alpha,
+              int warm, double* X, double* U, double* cost, int* status, int* iters, double* err, const AaOpt* aa,
+              int* aa_counts) {
     DevGuard dg_(c);
-    if (!c || !x0 || !scen || !X || !U || !cost || !status || !iters || !err) return fail(RAOCP_ERR_ARG, "null argument");
+    if (!c || !x0 || !scen || !X || !U || !cost || !status || !iters || !err || (aa && !aa_counts))
+        return fail(RAOCP_ERR_ARG, "null argument");
     if (B < 1 || B > 4096) return fail(RAOCP_ERR_ARG, "batch size must be in 1 .. 4096");
     if (T < 1) return fail(RAOCP_ERR_ARG, "the number of steps must be >= 1");
     if (max_iters < 0) return fail(RAOCP_ERR_ARG, "max_iters must be >= 0");
@@ -686,10 +720,29 @@ int raocp_cp_batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* 
         if (scen[q] < 0 || scen[q] >= nc)
             return fail(RAOCP_ERR_ARG, "scenario entry " + std::to_string(scen[q]) + " is not a child of the root (0 .. " +
                                            std::to_string(nc - 1) + ")");
+    int rc;
+    if (aa && ((rc = aa_check_opt(*aa)) || (rc = aa_check_ctx(c)))) return rc;
     c->bt.B = 0;
     c->bt.accel = false;
-    if (cpb_on(c)) return batch_mpc_kernel(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
+    if (aa || cpb_on(c))
+        return batch_mpc_kernel(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err, aa, aa_counts);
     return batch_mpc_seq(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err);
+}
+
+}  // namespace
+
+extern "C" {
+
+int raocp_cp_batch_mpc(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
+                       double alpha, int warm, double* X, double* U, double* cost, int* status, int* iters, double* err) {
+    return batch_mpc(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err, nullptr, nullptr);
+}
+
+int raocp_cp_batch_mpc_aa(raocp_ctx* c, int B, int T, const double* x0, const int* scen, int max_iters, double tol,
+                          double alpha, int warm, int accel, int accel_every, double accel_reg, double accel_safeguard,
+                          double* X, double* U, double* cost, int* status, int* iters, double* err, int* aa_counts) {
+    const AaOpt aa{accel, accel_every, accel_reg, accel_safeguard};
+    return batch_mpc(c, B, T, x0, scen, max_iters, tol, alpha, warm, X, U, cost, status, iters, err, &aa, aa_counts);
 }
 
 }  // extern "C"

@@ -1078,6 +1078,8 @@ std::string kernel_name(const raocp_ctx* c, int op) {
             return cpb_on(c) && !c->f32 ? raocp::cpa_name(raocp::cpb_tab_bytes(c->dev, false) > 0) : "";
         case 14:  // the step kernel of raocp_cp_batch_mpc ("" when the loop runs on the host)
             return cpb_on(c) ? raocp::mpc_step_name(c->f32) : "";
+        case 20:  // the step kernel of raocp_cp_batch_mpc_aa ("" where it refuses)
+            return cpb_on(c) && !c->f32 ? raocp::mpc_step_aa_name() : "";
         case 17:  // the kernels of raocp_evaluate and its number of sweep launches
             return raocp::eval_name(c->f32, (int)raocp::eval_sweep_plan(c->stage_ptr).size());
         case 18:  // the kernel of raocp_cp_batch_evaluate: the last batch's own form, else what a batch would run
@@ -1422,7 +1424,7 @@ int raocp_kernel_info(raocp_ctx* c, int op, char* buf, int cap) {
     DevGuard dg_(c);
     if (!c || !buf || cap < 1) return fail(RAOCP_ERR_ARG, "bad argument");
     const std::string s = kernel_name(c, op);
-    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16 && op != 18 && op != 19) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
+    if (s.empty() && op != 11 && op != 12 && op != 13 && op != 14 && op != 15 && op != 16 && op != 18 && op != 19 && op != 20) return fail(RAOCP_ERR_ARG, "unknown op " + std::to_string(op));
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RAOCP_OK;
 }

@@ -80,5 +80,11 @@ hipError_t cpb_launch(const Dev& p, const CpbArg& a, bool f32, hipStream_t strea
 const char* cpb_name(bool f32, bool lds_tabs);
 hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, bool f32, hipStream_t stream);
 const char* mpc_step_name(bool f32);
+// k_mpc_step_aa: k_mpc_step after a step that k_cpa solved (fp64 only). It also reduces the
+// instance's log rows 0 .. final_k to counts[b][t][kAaCounts] and, unless the step is the last,
+// leaves the instance's CpaState and G as the memset of a fresh accelerated batch does.
+hipError_t mpc_step_aa_launch(const Dev& p, const CpbArg& a, const MpcArg& m, const CpaArg& aa, int* counts,
+                              hipStream_t stream);
+const char* mpc_step_aa_name();
 
 }  // namespace raocp

@@ -886,8 +886,24 @@ __global__ void __launch_bounds__(kCpbBlock) k_cpa(Dev p, CpbArg a, CpaArg aa) {
 // step and every later one record status 2 (later ones: 0 iterations) and NaN for x+, u, l.
 // The plant step and the stage cost are computed in T; the records X, U, cost and err are double
 // for either T (widened at the store), status and iters int.
-template <class T>
-__global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg m) {
+//
+// k_mpc_step_aa (AA, fp64 only) is the same step after a solve of k_cpa, and in addition
+//   0. counts: the lanes stride over the records 0 .. final_k of the instance's log, each adds what
+//      aa_count (raocp_aa_ops.h) says to its four counters; a wave shuffle tree, then the four
+//      waves in index order from LDS, stored to counts[b][t]. An instance frozen at an earlier
+//      step stores zeros, the step that freezes it the counts of the solve that froze it.
+//   3. unless this was the last step: the instance's CpaState (pending flag and stored |r|_2
+//      included) and its G block are cleared with 16-B stores, so the next step's first k_cpa
+//      iteration sees what the memset of a fresh accelerated batch leaves: an empty history,
+//      whatever `warm` is. The last step leaves state and log in place for raocp_cp_batch_aa_log.
+// The iterate that is applied and carried over is Z[(final_k + 1) % 3] / E[(final_k + 1) % 2] as
+// after k_cpb: cpa_body decides `stop` before it considers a proposal, so the iteration that ends a
+// solve (through max_iters as through tol or a NaN) never writes one over g_k, and that slot holds
+// the last T(.) computed, which is also what it stores to u0 and what raocp_cp_batch_get reads.
+// (The arguments by value, as a kernel takes them: k_mpc_step<double> / <float> then keep the
+// resource lines they had before the body was shared, 40 / 24 VGPRs, 80 SGPRs, no scratch.)
+template <class T, bool AA>
+__device__ __forceinline__ void mpc_step_body(const Dev p, const CpbArg a, const MpcArg m, const CpaArg* aa, int* counts) {
     // 16 bytes of the slab: 2 doubles or 4 floats
     constexpr int VN = 16 / (int)sizeof(T);
     typedef T vt __attribute__((ext_vector_type(VN)));
@@ -908,6 +924,24 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
     const int frz = m.frz[b];
     cg<T> x = (cg<T>)(slab + a.lay.x0);
     if (t == 0 && tid < nx) Xo[tid] = (double)x[tid];
+    if constexpr (AA) {
+        __shared__ int s_cnt[kAaCounts][kCpbBlock / 64];
+        const int rows = frz >= 0 ? 0 : fk + 1;
+        cg<double> lg = (cg<double>)(aa->log + (size_t)b * a.hist_rows * kAaRec);
+        int cnt[kAaCounts] = {0, 0, 0, 0};
+        for (int r = tid; r < rows; r += nthr) aa_count((int)lg[(size_t)r * kAaRec], (int)lg[(size_t)r * kAaRec + 2], cnt);
+        _Pragma("unroll") for (int q = 0; q < kAaCounts; ++q) {
+            int c = cnt[q];
+            for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+            if ((tid & 63) == 0) s_cnt[q][tid >> 6] = c;
+        }
+        __syncthreads();
+        if (tid < kAaCounts) {
+            int c = s_cnt[tid][0];
+            for (int w = 1; w < (nthr >> 6); ++w) c += s_cnt[tid][w];
+            ((gl<int>*)counts)[bt * kAaCounts + tid] = c;
+        }
+    }
     if (frz >= 0 || (flags & 1)) {
         if (tid < nx) Xo[nx + tid] = qnan;
         if (tid < nu) Uo[tid] = qnan;
@@ -994,6 +1028,29 @@ __global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg 
         ctl->pad = 0;
         a.done[b] = 0;
     }
+    if constexpr (AA) {
+        // G (64 doubles) and the state block behind it (cpa_layout_dims). The other arrays are not
+        // cleared: cpa_body writes each of them before it sets the state field that lets it be
+        // read. dg / dr are read in the committed slots only (`count` of them; the slot `head`
+        // being pushed under `have` is taken from registers), pg / pr under `have`, sg under
+        // `pending`; all three fields are zero from here on.
+        typedef double v2 __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(1))) v2 glbv2;
+        const CpaSlab& A = aa->lay;
+        glbv2* g2 = (glbv2*)(aa->slab + (size_t)b * A.stride + A.G);
+        const long n2 = (A.state - A.G) / 2 + ((long)sizeof(CpaState) + 15) / 16;
+        const v2 z2 = 0.0;
+        for (long q = tid; q < n2; q += nthr) g2[q] = z2;
+    }
+}
+
+template <class T>
+__global__ void __launch_bounds__(kCpbBlock) k_mpc_step(Dev p, CpbArg a, MpcArg m) {
+    mpc_step_body<T, false>(p, a, m, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(kCpbBlock) k_mpc_step_aa(Dev p, CpbArg a, MpcArg m, CpaArg aa, int* counts) {
+    mpc_step_body<double, true>(p, a, m, &aa, counts);
 }
 
 // elements of the shared tables (sqrt Q, sqrt R, sqrt Pf and the four box tables)
@@ -1052,5 +1109,13 @@ hipError_t mpc_step_launch(const Dev& p, const CpbArg& a, const MpcArg& m, bool 
 }
 
 const char* mpc_step_name(bool f32) { return f32 ? "k_mpc_step<float>" : "k_mpc_step"; }
+
+hipError_t mpc_step_aa_launch(const Dev& p, const CpbArg& a, const MpcArg& m, const CpaArg& aa, int* counts,
+                              hipStream_t stream) {
+    k_mpc_step_aa<<<a.B, kCpbBlock, 0, stream>>>(p, a, m, aa, counts);
+    return hipGetLastError();
+}
+
+const char* mpc_step_aa_name() { return "k_mpc_step_aa"; }
 
 }  // namespace raocp

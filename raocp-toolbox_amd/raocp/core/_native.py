@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "raocp_reset_iterate", "raocp_kernel_info", "raocp_op_bench_rot",
     "raocp_cp_batch_run", "raocp_cp_batch_get", "raocp_cp_batch_first_inputs", "raocp_cp_batch_mpc",
     "raocp_evaluate", "raocp_cp_batch_evaluate", "raocp_cp_batch_run_aa", "raocp_cp_batch_aa_log", "raocp_cp_batch_get_prev",
+    "raocp_cp_batch_mpc_aa",
 ]
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -106,6 +107,8 @@ def load_library():
         "raocp_cp_batch_first_inputs": (c_int, [vp, vp]),
         "raocp_cp_batch_mpc": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_double, c_double, c_int,
                                        vp, vp, vp, vp, vp, vp]),
+        "raocp_cp_batch_mpc_aa": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_double, c_double, c_int,
+                                          c_int, c_int, c_double, c_double, vp, vp, vp, vp, vp, vp, vp]),
         "raocp_evaluate": (c_int, [vp, vp, c_int, vp, vp]),
         "raocp_cp_batch_evaluate": (c_int, [vp, vp]),
         "raocp_cp_prepare": (c_int, [vp, vp, c_int, c_double]),
@@ -416,11 +419,14 @@ class NativeContext:
         self._check(self._lib.raocp_cp_batch_first_inputs(self._h, _ptr(out)))
         return out[:B]
 
-    def cp_batch_mpc(self, x0, scen, max_iters, tol, alpha, warm=True):
+    def cp_batch_mpc(self, x0, scen, max_iters, tol, alpha, warm=True, accel=None):
         """Closed-loop simulation of a batch on the device: x0 is (B, nx), scen (B, T) integer
         indices into the root's children. Returns (X (B, T+1, nx), U (B, T, nu), cost (B, T),
         status (B, T), iters (B, T), err (B, T, 3)); afterwards cp_batch_get / cp_batch_first_inputs
-        describe every instance's last solve."""
+        describe every instance's last solve. accel = (m, every, reg, safeguard) solves every step
+        with the Anderson-accelerated kernel (raocp_cp_batch_mpc_aa) and returns a seventh array,
+        the (B, T, 4) counts of proposals, accepted trials, rejected trials and refused solves per
+        step; cp_batch_accel_log(b) then returns the log of instance b's last solve."""
         self._require_l()
         nx, nu = self._packed.nx, self._packed.nu
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
@@ -438,12 +444,25 @@ class NativeContext:
         status = np.zeros((b1, t1), dtype=np.int32)
         iters = np.zeros((b1, t1), dtype=np.int32)
         err = np.zeros((b1, t1, 3))
-        self._check(self._lib.raocp_cp_batch_mpc(
-            self._h, B, T, _ptr(x0), _ptr(scen) if scen.size else _ptr(np.zeros(1, dtype=np.int32)),
-            int(max_iters), float(tol), float(alpha), int(bool(warm)),
-            _ptr(X), _ptr(U), _ptr(cost), _ptr(status), _ptr(iters), _ptr(err)))
+        head = (self._h, B, T, _ptr(x0), _ptr(scen) if scen.size else _ptr(np.zeros(1, dtype=np.int32)),
+                int(max_iters), float(tol), float(alpha), int(bool(warm)))
+        tail = (_ptr(X), _ptr(U), _ptr(cost), _ptr(status), _ptr(iters), _ptr(err))
+        if accel is None:
+            self._check(self._lib.raocp_cp_batch_mpc(*head, *tail))
+            self._batch_B = B
+            return X, U, cost, status.astype(np.int64), iters.astype(np.int64), err
+        m, every, reg, safeguard = accel
+        counts = np.zeros((b1, t1, 4), dtype=np.int32)
+        self._check(self._lib.raocp_cp_batch_mpc_aa(*head, int(m), int(every), float(reg), float(safeguard), *tail,
+                                                    _ptr(counts)))
         self._batch_B = B
-        return X, U, cost, status.astype(np.int64), iters.astype(np.int64), err
+        # rows of every instance's last solve (a frozen instance: of the solve that froze it)
+        last = np.zeros(B, dtype=np.int32)
+        for b in range(B):
+            ran = np.flatnonzero(iters[b] > 0)
+            last[b] = iters[b, ran[-1]] if ran.size else 0
+        self._batch_iters = last
+        return X, U, cost, status.astype(np.int64), iters.astype(np.int64), err, counts.astype(np.int64)
 
     # ---- evaluation of a primal (include/raocp_hip.h raocp_evaluate)
     def evaluate(self, z=None, node_values=False):

@@ -20,8 +20,8 @@ import raocp.core.cache as cache
 import raocp.core.operators as ops
 import raocp.core.raocp_spec as spec
 
-__all__ = ["Solver", "normalise_initial_states", "normalise_scenarios", "sample_scenarios", "BatchSimulation",
-           "Evaluation"]
+__all__ = ["Solver", "normalise_initial_states", "normalise_scenarios", "sample_scenarios", "normalise_accel",
+           "BatchSimulation", "Evaluation"]
 
 
 def normalise_initial_states(initial_states, nx):
@@ -59,12 +59,32 @@ def sample_scenarios(probabilities, B, T, seed=None):
     return rng.choice(p.size, size=(B, T), p=p / p.sum()).astype(np.int32)
 
 
+def normalise_accel(accel, accel_every=1, accel_reg=1e-10, accel_safeguard=1.0):
+    """The acceleration options of chock_batch / simulate_batch as the native layer takes them:
+    None for accel = 0 (the plain solve), else (m, every, reg, safeguard) with 1 <= m <= 8. An
+    accel that is no integer in 0 .. 8, accel_every < 1 or a negative (or NaN) accel_reg /
+    accel_safeguard raises ValueError; nothing native is called."""
+    if not accel:
+        return None
+    if not (isinstance(accel, (int, np.integer)) and 1 <= accel <= 8):
+        raise ValueError(f"accel must be 0 or in 1 .. 8, got {accel!r}")
+    if int(accel_every) < 1 or not accel_reg >= 0.0 or not accel_safeguard >= 0.0:
+        raise ValueError("accel_every must be >= 1, accel_reg and accel_safeguard >= 0")
+    return int(accel), int(accel_every), float(accel_reg), float(accel_safeguard)
+
+
+_ACCEL_REFUSED = ("accel > 0 needs the fp64 batch kernel: not available on a float32 solver, "
+                  "a sharded context or a context the batch kernel does not cover")
+
+
 class BatchSimulation:
     """The result of Solver.simulate_batch: states (B, T+1, nx), inputs (B, T, nu),
     stage_costs (B, T), status (B, T), iterations (B, T), errors (B, T, 3) and the realised
-    scenarios (B, T)."""
+    scenarios (B, T). accel_counts is None for a plain simulation; for accel=m it is the (B, T, 4)
+    int array of what the acceleration did in each step's solve: proposals made, trials accepted,
+    trials rejected, solves refused (zero for the steps a frozen instance did not solve)."""
 
-    def __init__(self, states, inputs, stage_costs, status, iterations, errors, scenarios):
+    def __init__(self, states, inputs, stage_costs, status, iterations, errors, scenarios, accel_counts=None):
         self.states = states
         self.inputs = inputs
         self.stage_costs = stage_costs
@@ -72,6 +92,7 @@ class BatchSimulation:
         self.iterations = iterations
         self.errors = errors
         self.scenarios = scenarios
+        self.accel_counts = accel_counts
 
 
 class Evaluation:
@@ -221,23 +242,16 @@ class Solver:
         accepted, 3 trial rejected, 4 solve refused), column count, what followed (0 nothing, 1 a
         proposal, 2 a refused solve), ||r||_2, gamma[8]. accel=0 (the default) is the plain solve.
         Out of scope: a float32 solver, a sharded context and a context the batch kernel does not
-        cover raise ValueError for accel > 0 (there is no sequential fallback); simulate_batch and
-        the single-solve chock are not accelerated; warm=True after an accelerated batch continues
-        from its iterate with an empty history."""
+        cover raise ValueError for accel > 0 (there is no sequential fallback); the single-solve
+        chock is not accelerated; warm=True after an accelerated batch continues from its iterate
+        with an empty history."""
         nx = self.__raocp.state_dynamics_at_node(1).shape[1]
         x0 = normalise_initial_states(initial_states, nx)
         B = x0.shape[0]
         native = self.__cache.native
-        aa = None
-        if accel:
-            if not (isinstance(accel, (int, np.integer)) and 1 <= accel <= 8):
-                raise ValueError(f"accel must be 0 or in 1 .. 8, got {accel!r}")
-            if int(accel_every) < 1 or not accel_reg >= 0.0 or not accel_safeguard >= 0.0:
-                raise ValueError("accel_every must be >= 1, accel_reg and accel_safeguard >= 0")
-            if native.kernel_info(19) == "":
-                raise ValueError("accel > 0 needs the fp64 batch kernel: not available on a float32 solver, "
-                                 "a sharded context or a context the batch kernel does not cover")
-            aa = (int(accel), int(accel_every), float(accel_reg), float(accel_safeguard))
+        aa = normalise_accel(accel, accel_every, accel_reg, accel_safeguard)
+        if aa and native.kernel_info(19) == "":
+            raise ValueError(_ACCEL_REFUSED)
         z0 = e0 = None
         if warm:
             if B != self.__batch_size:
@@ -266,7 +280,7 @@ class Solver:
 
     # ----- closed-loop simulation of a batch (extension), resident on the device
     def simulate_batch(self, initial_states, num_steps, scenarios=None, seed=None, max_iters=10, tol=1e-5,
-                       step_size=None, warm=True):
+                       step_size=None, warm=True, accel=0, accel_every=1, accel_reg=1e-10, accel_safeguard=1.0):
         """Closed-loop MPC over num_steps steps for B initial states at once: every step solves
         each instance from its current state, applies the root's input and moves the plant along
         the realised scenario (x+ = A_i x + B_i u_0 for the root's child i); warm=True starts each
@@ -276,10 +290,24 @@ class Solver:
         (also kept as `batch_simulation`); afterwards batch_primal_flat(b), batch_dual_flat(b)
         and batch_first_inputs() describe every instance's last solve. If a NaN reached a box
         projection in some instances, those are frozen from that step on, the results are
-        stored and ValueError names them."""
+        stored and ValueError names them.
+
+        accel=m (1 <= m <= 8) solves every step of every instance with the Anderson-accelerated
+        kernel, with the algorithm and the options of chock_batch(accel=m). Every step starts with
+        an empty acceleration history whatever `warm` is (a new state is a new fixed-point map);
+        warm=True still carries the iterate over. The result's accel_counts is then the (B, T, 4)
+        int array of proposals made, trials accepted, trials rejected and solves refused per step,
+        and batch_accel_log[b] the log of instance b's last solve. accel=0 (the default) is the
+        plain simulation; accel_counts is None. Out of scope: a float32 solver, a sharded context
+        and a context the batch kernel does not cover raise ValueError for accel > 0 (there is no
+        sequential fallback and no float form)."""
         nx = self.__raocp.state_dynamics_at_node(1).shape[1]
         x0 = normalise_initial_states(initial_states, nx)
         B, T = x0.shape[0], int(num_steps)
+        native = self.__cache.native
+        aa = normalise_accel(accel, accel_every, accel_reg, accel_safeguard)
+        if aa and native.kernel_info(20) == "":
+            raise ValueError(_ACCEL_REFUSED)
         tree = self.__raocp.tree
         if scenarios is None:
             scen = sample_scenarios(tree.conditional_probabilities_of_children(0), B, T, seed)
@@ -291,12 +319,18 @@ class Solver:
             self.__parameter_1 = self.__parameter_2 = float(step_size)
         print("timer started")
         tick = time.perf_counter()
-        X, U, cost, status, iters, err = self.__cache.native.cp_batch_mpc(x0, scen, int(max_iters), float(tol),
-                                                                          self.__parameter_1, warm)
+        counts = None
+        if aa:
+            X, U, cost, status, iters, err, counts = native.cp_batch_mpc(x0, scen, int(max_iters), float(tol),
+                                                                         self.__parameter_1, warm, accel=aa)
+        else:
+            X, U, cost, status, iters, err = native.cp_batch_mpc(x0, scen, int(max_iters), float(tol),
+                                                                 self.__parameter_1, warm)
         tock = time.perf_counter()
         print(f"timer stopped in {tock - tick:0.4f} seconds")
         self.__batch_size = B
-        self.batch_simulation = BatchSimulation(X, U, cost, status, iters, err, scen)
+        self.batch_simulation = BatchSimulation(X, U, cost, status, iters, err, scen, counts)
+        self.batch_accel_log = [native.cp_batch_accel_log(b) for b in range(B)] if aa else []
         bad = [int(b) for b in np.flatnonzero((status == 2).any(axis=1))]
         if bad:
             step = [int(np.argmax(status[b] == 2)) for b in bad]

@@ -12,6 +12,18 @@ bracketed with raocp_device_synchronize, one discarded warm-up run, the median o
 section 7). Prints one JSON object; --out FILE also writes it there.
 
     python tools/mpc_bench.py [--legs resident,host_loop] [--B 16,256,1024] [--out FILE]
+
+--accel M (1 .. 8; off by default) measures something else with the same protocol (the same x0
+distribution, seeded paths, pinned alpha, warm starts, one discarded run and the median of --reps
+between raocp_device_synchronize calls): one cp_batch_mpc call per leg,
+  plain      k_cpb + k_mpc_step, as `resident` above
+  accel      k_cpa with memory M + k_mpc_step_aa (a trial every iteration, reg 1e-10, safeguard 1)
+both at --tol (default 0: every solve runs K + 1 iterations). Per B and leg it reports the wall
+time, the fraction of instances converged (status 0) at each step, the iterations of a solve
+(min / median / max over all B x T solves and the median per step) and, for `accel`, the totals
+of accel_counts (proposals, trials accepted, trials rejected, solves refused). --legs is ignored.
+
+    python tools/mpc_bench.py --accel 5 [--tol 1e-5] [--K 50] [--B 256] [--out FILE]
 """
 import argparse
 import contextlib
@@ -39,6 +51,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--accel", type=int, default=0)
+    ap.add_argument("--tol", type=float, default=0.0, help="with --accel only")
     a = ap.parse_args()
     if a.dtype == "float32":
         # the float kernels are opt-in; RAOCP_CPB=0 still selects the host loop over sequential solves
@@ -87,6 +101,41 @@ def main():
             x = np.einsum("brk,bk->br", A[j], x) + np.einsum("brk,bk->br", Bm[j], u)
             out.append(x)
         return np.stack(out, axis=1)
+
+    def solves(out):
+        """What a run's solves did: out = cp_batch_mpc's tuple."""
+        status, iters = out[3], out[4]
+        d = {"converged_fraction_per_step": [float(v) for v in np.mean(status == 0, axis=0)],
+             "iterations": {"min": int(iters.min()), "median": float(np.median(iters)), "max": int(iters.max())},
+             "iterations_median_per_step": [float(v) for v in np.median(iters, axis=0)]}
+        if len(out) > 6:
+            d["accel_counts_total"] = dict(zip(("proposals", "accepted", "rejected", "refused"),
+                                               (int(v) for v in out[6].sum(axis=(0, 1)))))
+        return d
+
+    if a.accel:
+        aa = (a.accel, 1, 1e-10, 1.0)
+        res["accel"] = {"m": a.accel, "every": 1, "reg": 1e-10, "safeguard": 1.0, "tol": a.tol}
+        res["legs"] = {"plain": {}, "accel": {}}
+        for B in [int(v) for v in a.B.split(",")]:
+            rng = np.random.default_rng(B)
+            X = x0[None, :] * (0.1 + rng.random((B, 1)))
+            scen = sample_scenarios(tree.conditional_probabilities_of_children(0), B, T, seed=B)
+            fns = {"plain": lambda: nat.cp_batch_mpc(X, scen, K, a.tol, alpha, True),             # noqa: E731
+                   "accel": lambda: nat.cp_batch_mpc(X, scen, K, a.tol, alpha, True, accel=aa)}   # noqa: E731
+            for leg, fn in fns.items():
+                sec = timed(fn)
+                d = {"seconds": sec, "ms_per_step": 1e3 * sec / T}
+                d.update(solves(fn()))
+                res["legs"][leg][str(B)] = d
+        res["kernels"] = [nat.kernel_info(op) for op in (13, 14, 19, 20)]
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
 
     legs = a.legs.split(",")
     for leg in legs:
