@@ -5,10 +5,12 @@
 //           j = 1 .. 8 against the same algorithm in long double: forward error <= 1e-12
 //           (kappa j eps ~ 1e-13) and backward error <= 1e-14 (|G||gamma| + |b|) (j eps ~ 1e-15)
 //   refuse: an indefinite G, a zero G, a NaN in b, j = 0 and j = 9 return false
+//   reginf: reg = +inf refuses for j = 1, 4 and 8, on an SPD G the default reg solves and on a zero G
 //   layout: every array on 16 B, the stride on 256 B, no two arrays overlap, all inside the stride
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <limits>
 #include <vector>
 
 #include "raocp_aa_ops.h"
@@ -112,6 +114,26 @@ int main() {
         const bool r6 = raocp::aa_solve(2, I, b, reg, gam, Lw);  // and the identity is solved
         const bool ok = !r1 && !r2 && !r3 && !r4 && !r5 && r6 && std::fabs(gam[0] - 1.0 / (1.0 + reg)) <= 1e-15;
         std::printf("refuse indefinite=%d zero=%d nan=%d j0=%d j9=%d identity=%d %s\n", r1, r2, r3, r4, r5, r6, ok ? "ok" : "FAIL");
+        bad += !ok;
+    }
+    {
+        // reg = +inf: the shift is inf (tr > 0) or NaN (tr == 0), so the first pivot refuses
+        const double inf = std::numeric_limits<double>::infinity();
+        const int js[3] = {1, 4, kAaMaxM};
+        bool r[3], z[3];
+        for (int q = 0; q < 3; ++q) {
+            const int j = js[q];
+            double G[kAaMaxM * kAaMaxM] = {0}, Z[kAaMaxM * kAaMaxM] = {0}, Lw[kAaMaxM * kAaMaxM], b[kAaMaxM], gam[kAaMaxM];
+            for (int a = 0; a < j; ++a) {
+                b[a] = rnd();
+                for (int c = 0; c <= a; ++c) G[a * kAaMaxM + c] = G[c * kAaMaxM + a] = (a == c ? 2.0 + j : 0.0) + 0.5 * rnd();
+            }
+            const bool solved = raocp::aa_solve(j, G, b, reg, gam, Lw);  // the same system is solved with the default
+            r[q] = raocp::aa_solve(j, G, b, inf, gam, Lw) || !solved;
+            z[q] = raocp::aa_solve(j, Z, b, inf, gam, Lw);  // tr = 0: inf * 0
+        }
+        const bool ok = !r[0] && !r[1] && !r[2] && !z[0] && !z[1] && !z[2];
+        std::printf("reginf j1=%d j4=%d j8=%d zero1=%d zero4=%d zero8=%d %s\n", r[0], r[1], r[2], z[0], z[1], z[2], ok ? "ok" : "FAIL");
         bad += !ok;
     }
     {

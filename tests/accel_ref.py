@@ -24,7 +24,9 @@ def aa_system(dR, r, reg):
     G = A @ A.T
     b = A @ r
     j = len(dR)
-    return G + reg * (np.trace(G) / j) * np.eye(j), b
+    Gb = G.copy()
+    Gb[np.diag_indices(j)] += reg * (np.trace(G) / j)   # the diagonal only: reg = inf leaves the rest finite
+    return Gb, b
 
 
 def aa_solve(Gb, b):

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from raocp.problems import build_problem, recipe_from_npz, recipe_general, recipe_synthetic
+from raocp.problems import build_problem, recipe_from_npz, recipe_general, recipe_general_small, recipe_synthetic
 from helpers import crafted_rotations, crafted_start
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -34,6 +34,10 @@ BATCH_SEEDS = {"main": (32, 37, 50), "bin6": (1, 2, 3), "c1n5": (5, 12, 46), "m7
 BATCH_KERNEL = {"main": ("k_cpb<true>", "k_cpb<float, true>"), "bin6": ("k_cpb<true>", "k_cpb<float, true>"),
                 "c1n5": ("k_cpb<true>", "k_cpb<float, true>"), "m7x32": ("k_cpb<false>", "k_cpb<float, false>"),
                 "m7x32-dense": ("k_cpb<false>", "k_cpb<float, false>")}
+# the form of the accelerated batch kernel (kernel_info(19), fp64 only) on the trees of
+# tests/accel_cases.py: the same rule, so only the 75 KB of m7x32's tables are read from HBM
+CPA_KERNEL = {"main": "k_cpa<true>", "s1x1": "k_cpa<true>", "s5x3": "k_cpa<true>", "s17x5": "k_cpa<true>",
+              "s16x16": "k_cpa<true>", "g53": "k_cpa<true>", "m7x32": "k_cpa<false>", "m7x32-dense": "k_cpa<false>"}
 ENTRY_SEEDS = {"bin7": 1, "main": 22}  # the stand-alone entry points project the crafted dual itself
 T_OFFSET = 50.0
 ITERS = (0, 2)  # max_iters of the two runs of every case: one iteration, three iterations
@@ -92,6 +96,7 @@ _TREES = {
     "tern32d4": lambda: _synthetic(3, 4, 32, 12, 4),   # 121 nodes
     "quad64d3": lambda: _synthetic(4, 3, 64, 16, 7),   # 85 nodes
     "m7x32": _seven_modes,                             # 31 nodes, tables beyond the batch kernel's LDS
+    "g53": lambda: recipe_general_small("g53"),        # 27 nodes, 1 / 2 / 3 children, 5 / 3
 }
 
 

@@ -8,7 +8,10 @@ must be bit-identical to chock_batch(states[:, t], accel=m) started from the rep
 final iterate (warm) or from zero. The replay is fed the device's recorded states, so nothing
 compounds and every comparison is array_equal; the per-step counts are compared with a NumPy count
 of the replay's log. Every problem comes from the committed fixtures; B = 3, T = 3 unless a test
-says otherwise.
+says otherwise. Section 8 repeats the replay with memories 1 and 8 and a cadence of 3, on a ternary
+tree with dense weights and on the tree whose tables k_cpa<false> reads from HBM
+(tests/branch_cases.py), and runs a simulation whose every solve is refused (accel_reg = inf): the
+plain simulation bit for bit, with the fourth counter a closed form of the iteration count.
 """
 import contextlib
 import os
@@ -16,6 +19,9 @@ import os
 import numpy as np
 import pytest
 
+import accel_cases as ac
+import accel_ref
+import branch_cases as bc
 import raocp.core as core
 from raocp.core._native import RaocpError
 from helpers import problem_from_golden
@@ -69,9 +75,9 @@ def counts_of_log(log):
 class Run:
     """One resident run with what the solver reports about every instance's last solve."""
 
-    def __init__(self, m, X, scen, K, tol, warm, raises=False, **aa):
+    def __init__(self, m, X, scen, K, tol, warm, raises=False, accel=5, **aa):
         s = core.Solver(problem_spec=m["prob"])
-        kw = dict(scenarios=scen, max_iters=K, tol=tol, step_size=m["alpha"], warm=warm, accel=5, **aa)
+        kw = dict(scenarios=scen, max_iters=K, tol=tol, step_size=m["alpha"], warm=warm, accel=accel, **aa)
         if raises:
             with pytest.raises(ValueError) as ei:
                 s.simulate_batch(X, scen.shape[1], **kw)
@@ -99,8 +105,8 @@ def _rows(solver, B):
     return np.array([np.atleast_2d(solver.batch_error_cache[b]).shape[0] for b in range(B)])
 
 
-def _assert_replay_bitwise(m, run, K, tol, warm, **aa):
-    """Every step of the resident run against a host-driven chock_batch(accel=5) from the device's
+def _assert_replay_bitwise(m, run, K, tol, warm, accel=5, **aa):
+    """Every step of the resident run against a host-driven chock_batch(accel=m) from the device's
     recorded state; returns the replay's per-step logs."""
     res = run.res
     B, T = res.scenarios.shape
@@ -109,7 +115,7 @@ def _assert_replay_bitwise(m, run, K, tol, warm, **aa):
     logs = []
     for t in range(T):
         st = rep.chock_batch(res.states[:, t], max_iters=K, tol=tol, step_size=m["alpha"], warm=warm and t > 0,
-                             accel=5, **aa)
+                             accel=accel, **aa)
         assert np.array_equal(res.status[:, t], st), t
         assert np.array_equal(res.iterations[:, t], _rows(rep, B)), t
         assert np.array_equal(res.errors[:, t], _last_rows(rep, B)), t
@@ -341,3 +347,93 @@ def test_accel_zero_is_the_plain_simulation_and_refusals(golden):
         a.simulate_batch(m["X"], 3, accel=5, accel_every=0, **kw)
     # nothing of the refused calls replaced the last result
     assert a.batch_simulation is ra
+
+
+# ---- 8. other memories, cadences and trees; every solve refused; a context without the kernels
+
+def _tree_problem(tree):
+    """_problem for a tree of tests/branch_cases.py: its alpha (pinned or the oracle's own), x0, 0.5 x0
+    and -0.3 x0, scenario paths over the root's children the way _problem builds them."""
+    key = ("tree", tree)   # _problem's entries (by fixture name) hold no oracle
+    if key not in _PROB:
+        r, prob, op, alpha = bc.problem(tree)
+        x0 = np.asarray(r["x0"], dtype=float).reshape(-1)
+        nc = len(prob.tree.children_of(0))
+        scen = np.array([[(b + t) % nc for t in range(3)] for b in range(3)], dtype=np.int64)
+        assert set(scen.reshape(-1)) == set(range(nc))
+        _PROB[key] = dict(prob=prob, orc=op, x0=x0, alpha=alpha, nc=nc, X=np.stack([x0, 0.5 * x0, -0.3 * x0]), scen=scen)
+    return _PROB[key]
+
+
+GRID = [("main", 1, 1), ("main", 8, 1), ("main", 3, 3), ("s5x3", 8, 1), ("m7x32", 8, 1)]
+
+
+@pytest.mark.parametrize("warm", [True, False])
+@pytest.mark.parametrize("tree,accel,every", GRID)
+def test_replay_bitwise_over_memories_cadences_and_trees(tree, accel, every, warm):
+    """The replay of section 2 with the degenerate ring (1), the full one (8: with K = 30 it fills
+    and wraps in every step) and a cadence of 3, and with memory 8 on a ternary tree with dense
+    weights per mode and on the 7-mode tree whose tables k_cpa<false> reads from HBM."""
+    m = _tree_problem(tree)
+    run = Run(m, m["X"], m["scen"], 30, 0.0, warm, accel=accel, accel_every=every)
+    nat = run.solver.cache.native
+    assert nat.kernel_info(19) == bc.CPA_KERNEL[tree] and nat.kernel_info(20) == "k_mpc_step_aa"
+    assert np.all(run.res.iterations == 31) and np.all(run.res.status == 1)
+    logs = _assert_replay_bitwise(m, run, 30, 0.0, warm, accel=accel, accel_every=every)
+    c = run.res.accel_counts
+    print(tree, accel, every, warm, "accel_counts", c.tolist())
+    assert np.all(c[:, :, 0] >= 1) and np.all(c[:, :, 3] == 0)      # proposals in every step of every instance
+    for b in range(3):   # step 0 is the cold solve from X: the ring fills (tests/test_accel_host.py, the free model)
+        assert logs[0][b][:, 1].max() == accel and c[b, 0, 0] >= 5, (b, logs[0][b][:, :3].astype(int).tolist())
+    if every > 1:        # a proposal only where (k + 1) % every == 0
+        off = [k for k in range(31) if (k + 1) % every]
+        assert not any(logs[t][b][off, 2].any() for t in range(3) for b in range(3))
+
+
+@pytest.mark.parametrize("warm", [True, False])
+@pytest.mark.parametrize("tree", ["main", "s5x3", "m7x32"])
+def test_every_solve_refused_is_the_plain_simulation_bitwise(tree, warm):
+    """accel_reg = inf: aa_solve refuses every system at its first pivot, so every step is the plain
+    step and the fourth counter is the only one that moves. With a trial every iteration a solve
+    of n iterations refuses at every odd k below its stopping record: (n - 1) // 2 times
+    (accel_cases.refusals_of), whatever the trajectory; the free model says the same."""
+    m = _tree_problem(tree)
+    run = Run(m, m["X"], m["scen"], 30, 0.0, warm, accel=5, accel_reg=float("inf"))
+    plain = core.Solver(problem_spec=m["prob"])
+    rp = plain.simulate_batch(m["X"], 3, scenarios=m["scen"], max_iters=30, tol=0.0, step_size=m["alpha"], warm=warm)
+    for f in FIELDS[:-1] + ("scenarios",):
+        assert np.array_equal(getattr(run.res, f), getattr(rp, f)), f
+    for b in range(3):
+        assert np.array_equal(run.fin[b][0], plain.batch_primal_flat(b)) and np.array_equal(run.fin[b][1], plain.batch_dual_flat(b))
+    assert np.array_equal(run.first, plain.batch_first_inputs())
+    c = run.res.accel_counts
+    print(tree, warm, "accel_counts", c.tolist())
+    assert np.all(c[:, :, 0:3] == 0)
+    assert np.all(run.res.iterations == 31) and ac.refusals_of(31, 1) == 15
+    assert np.array_equal(c[:, :, 3], (run.res.iterations - 1) // 2) and np.all(c[:, :, 3] == 15)
+    ref = accel_ref.run(m["orc"], m["X"][0], m["alpha"], 30, 0.0, m=5, reg=float("inf"))
+    assert np.array_equal(counts_of_log(ref.log), [0, 0, 0, 15])
+    for b in range(3):   # the last step's log: the model's records but for |r|_2, which no decision reads here
+        assert np.array_equal(run.logs[b][:, :3], ref.log[:, :3]) and not run.logs[b][:, 4:].any()
+        assert np.array_equal(c[b, -1], counts_of_log(run.logs[b]))
+
+
+def test_a_context_the_batch_kernel_does_not_cover_has_no_accelerated_form():
+    """s6x18: nu = 18 is beyond the 16 inputs k_cpb covers, so the plain calls fall back to the
+    sequential solves and the accelerated ones, which have no such form, refuse before any launch."""
+    r, prob, op, alpha = bc.problem("s6x18")
+    s = core.Solver(problem_spec=prob)
+    nat = s.cache.native
+    assert nat.kernel_info(19) == nat.kernel_info(20) == "" and nat.kernel_info(13) == ""
+    x0 = np.asarray(r["x0"], dtype=float).reshape(-1)
+    X = np.stack([x0, 0.5 * x0])
+    scen = np.zeros((2, 2), dtype=np.int64)
+    with pytest.raises(ValueError):
+        s.chock_batch(X, 5, 0.0, alpha, accel=5)
+    with pytest.raises(ValueError):
+        s.simulate_batch(X, 2, scenarios=scen, max_iters=5, tol=0.0, step_size=alpha, accel=5)
+    with pytest.raises(RaocpError):
+        nat.cp_batch_run(X, 5, 0.0, alpha, accel=(5, 1, 1e-10, 1.0))
+    with pytest.raises(RaocpError):
+        nat.cp_batch_mpc(X, scen, 5, 0.0, alpha, accel=(5, 1, 1e-10, 1.0))
+    assert s.batch_error_cache == [] and s.batch_simulation is None
