@@ -25,10 +25,16 @@ GOLDEN_FILE = {"main": "main_trace", "bin6": "traj_small", "c1n5": "traj_small"}
 SEED = 1
 SEEDS = {"main": 32, "c1n5": 5,
          # the shape sweep's small cones (nx = 1, 5, 6): the smallest seed that qualifies
-         "s1x1": 82, "s1x1u": 82, "s5x3": 3, "s5x3u": 3, "s6x18": 3, "s6x18u": 3}
+         "s1x1": 82, "s1x1u": 82, "s5x3": 3, "s5x3u": 3, "s6x18": 3, "s6x18u": 3,
+         # the wide trees (5 / 3: cones of 6 to 9 entries, 280 to 600 of them on w5 and w17)
+         "w5": 110, "w5u": 163, "w17": 207, "w17u": 2700, "r12": 2, "r12u": 2, "w64r": 3, "w64ru": 6,
+         "w65r": 4, "w65ru": 4, "w82r": 2, "w82ru": 2}
 # one start per instance of a batch
 BATCH_SEEDS = {"main": (32, 37, 50), "bin6": (1, 2, 3), "c1n5": (5, 12, 46), "m7x32": (1, 2, 3),
                "m7x32-dense": (1, 2, 3)}
+# the wide trees' batch starts: three seeds where one start covers the tree, one
+# seed whose three rotations are the three instances where it takes the three (ROTATIONS)
+WIDE_BATCH_SEEDS = {"w5": (110, 163, 183), "w17": (207, 953, 1162), "r12": (2,), "w65r": (4,)}
 # the form of the batch kernel each problem reaches (kernel_info(13)), fp64 / fp32: the tables of the
 # golden problems fit the kernel's LDS budget and are staged there, those of m7x32 are read from HBM
 BATCH_KERNEL = {"main": ("k_cpb<true>", "k_cpb<float, true>"), "bin6": ("k_cpb<true>", "k_cpb<float, true>"),
@@ -125,6 +131,54 @@ for _nx, _nu in SHAPES:
 SHAPE_TREES = tuple(shape_tree(nx, nu, sh) for nx, nu in SHAPES for sh in (False, True))
 
 
+# ---- wide branching: 5 to 82 children per node, where no `<= 4` fast path
+# applies and the lane groups sized by cmax span one to several waves. name -> (modes, kind, N, nx,
+# nu, alpha_r): "full": v uniform, P uniform and full (every node has `modes` children); "ragged": v
+# uniform, row i of P has 1 + (7 i mod modes) successors i, i + 1, .. with random weights (1 .. 12
+# children at 12 modes); "root": v uniform, P[i] = 1/2 on i and i + 1 (a wide root over binary stages).
+# Each has two trees of recipe_general like the shape sweep: a dense weight table per mode, and "<name>u"
+# with one table over the modes. w83r is one past the admitted maximum (check_group: 257 lanes).
+# CPU only so far (the census of their starts, the oracle's golden pins): raocp_ctx_create does not survive a
+# root of five or more children, so no GPU test creates a context on them yet.
+_WIDE = {"w5": (5, "full", 3, 5, 3, 0.1), "w8": (8, "full", 2, 20, 8, 0.7), "w17": (17, "full", 2, 5, 3, 0.99),
+         "r12": (12, "ragged", 2, 17, 5, 0.1), "w64r": (64, "root", 2, 5, 3, 0.7), "w65r": (65, "root", 2, 5, 3, 0.99),
+         "w82r": (82, "root", 2, 5, 3, 0.1), "w8s": (8, "full", 2, 5, 3, 0.7), "w83r": (83, "root", 2, 5, 3, 0.1)}
+WIDE = ("w5", "w8", "w17", "r12", "w64r", "w65r", "w82r")
+WIDE_NODES = {"w5": 156, "w8": 73, "w17": 307, "r12": 91, "w64r": 193, "w65r": 196, "w82r": 247}
+
+
+def wide_chain(M, kind, seed):
+    """(P, v) of a wide tree's Markov chain (see _WIDE)."""
+    v = np.full(M, 1.0 / M)
+    if kind == "full":
+        return np.full((M, M), 1.0 / M), v
+    P = np.zeros((M, M))
+    if kind == "root":
+        for i in range(M):
+            P[i, i] = P[i, (i + 1) % M] = 0.5
+        return P, v
+    assert kind == "ragged", kind
+    rng = np.random.default_rng([seed, 2])
+    for i in range(M):
+        k = 1 + (7 * i) % M
+        w = rng.uniform(0.5, 1.5, k)
+        P[i, (i + np.arange(k)) % M] = w / w.sum()
+    return P, v
+
+
+def _wide_recipe(name, shared):
+    M, kind, N, nx, nu, alpha_r = _WIDE[name]
+    seed = 1000 + sum(map(ord, name))
+    P, v = wide_chain(M, kind, seed)
+    return recipe_general(P, v, N, N, nx, nu, seed=seed, alpha_r=alpha_r, shared_weights=shared)
+
+
+for _name in _WIDE:
+    for _sh in (False, True):
+        _TREES[_name + ("u" if _sh else "")] = functools.partial(_wide_recipe, _name, _sh)
+WIDE_TREES = tuple(t + s for t in WIDE for s in ("", "u"))
+
+
 @functools.lru_cache(maxsize=None)
 def problem(tree):
     """(recipe, RAOCP problem, OracleProblem, alpha) of a tree, built once. alpha: the golden
@@ -158,8 +212,18 @@ def seed_of(tree):
     return SEEDS.get(tree, SEEDS.get(tree.partition("-")[0], SEED))
 
 
+# The wide root of w64r / w65r / w82r is the only parent with a child slot >= 2, and slot 11 of r12
+# has two parents: one start gives such a slot one class, so these take the three rotated starts (every
+# cone takes each class once), like the trees too small for the 30 % shares.
+ROTATIONS = {t + s: 3 for t in ("r12", "w64r", "w65r", "w82r") for s in ("", "u")}
+
+
+# their 250 to 400 cones of 6 to 9 entries: see helpers.crafted_start
+CALM = frozenset(ROTATIONS) - {"r12", "r12u"}
+
+
 def rotations(tree):
-    return crafted_rotations(problem(tree)[2])
+    return ROTATIONS.get(tree, crafted_rotations(problem(tree)[2]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -167,7 +231,7 @@ def start(tree, rot, seed, f32=False):
     """(p0, d0, child classes, leaf classes) of the tree's crafted start, read-only. f32: the
     start rounded to float, which is what a float context holds after set_primal / set_dual."""
     r, prob, op, alpha = problem(tree)
-    p0, d0, ccls, lcls = crafted_start(op, alpha, seed, T_OFFSET, rot)
+    p0, d0, ccls, lcls = crafted_start(op, alpha, seed, T_OFFSET, rot, calm=tree in CALM)
     if f32:
         p0, d0 = p0.astype(np.float32).astype(np.float64), d0.astype(np.float32).astype(np.float64)
     for a in (p0, d0, ccls, lcls):
@@ -515,4 +579,5 @@ def shard_cuts(tree):
 
 # every (tree, seed) some CP loop on the GPU starts from: the census test covers them all
 CENSUS_CASES = sorted({(c[1], seed_of(c[1])) for c in FAMILIES} | {(t, s) for t in BATCH_TREES for s in BATCH_SEEDS[t]} |
-                      {(t, seed_of(t)) for t in SHAPE_TREES} | {(t, shard_seed_of(t)) for t in SHARD_TREES})
+                      {(t, seed_of(t)) for t in SHAPE_TREES} | {(t, shard_seed_of(t)) for t in SHARD_TREES} |
+                      {(t, seed_of(t)) for t in WIDE_TREES} | {(t, s) for t in WIDE_BATCH_SEEDS for s in WIDE_BATCH_SEEDS[t]})

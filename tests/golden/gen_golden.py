@@ -8,6 +8,7 @@ fixtures the test-suite and the oracle are pinned against.
     python -B tests/golden/gen_golden.py            # writes tests/golden/*.npz
     python -B tests/golden/gen_golden.py warm       # only warm_start.npz
     python -B tests/golden/gen_golden.py general    # only general_kat.npz
+    python -B tests/golden/gen_golden.py wide       # only wide_kat.npz
 
 The reference needs `turtle` (tkinter) and `tikzplotlib`, both absent here:
 they are stubbed as empty modules (scenario_tree.py:4, solver.py:8 import them
@@ -162,6 +163,38 @@ def recipe_g618():
 
 
 GENERAL = (("g53", recipe_g53), ("g175", recipe_g175), ("g618", recipe_g618))
+
+
+def wide_chain(M, kind, seed):
+    """tests/branch_cases.py wide_chain, restated: v uniform; "full": P uniform; "ragged": row i has
+    1 + (7 i mod M) successors i, i + 1, .. with weights from default_rng([seed, 2])."""
+    v = np.full(M, 1.0 / M)
+    if kind == "full":
+        return np.full((M, M), 1.0 / M), v
+    P = np.zeros((M, M))
+    rng = np.random.default_rng([seed, 2])
+    for i in range(M):
+        k = 1 + (7 * i) % M
+        w = rng.uniform(0.5, 1.5, k)
+        P[i, (i + np.arange(k)) % M] = w / w.sum()
+    return P, v
+
+
+def recipe_w8s():
+    """(5, 3), 8 modes, full, N = 2: 73 nodes, 8 children per node (branch_cases "w8s")."""
+    seed = 1000 + sum(map(ord, "w8s"))
+    P, v = wide_chain(8, "full", seed)
+    return recipe_general(P, v, 2, 2, 5, 3, seed=seed, alpha_r=0.7)
+
+
+def recipe_r12():
+    """(17, 5), 12 modes, 1 .. 12 children, N = 2: 91 nodes (branch_cases "r12")."""
+    seed = 1000 + sum(map(ord, "r12"))
+    P, v = wide_chain(12, "ragged", seed)
+    return recipe_general(P, v, 2, 2, 17, 5, seed=seed, alpha_r=0.1)
+
+
+WIDE = (("w8s", recipe_w8s), ("r12", recipe_r12))
 
 
 def recipe_bin6():
@@ -437,6 +470,27 @@ def gen_general(out):
         run_chock(name, rf(), 14, 0.0, out)
 
 
+def gen_wide(out):
+    """5 to 12 children per node (the oracle is otherwise pinned on at most 3): the tree factory's
+    outputs, L and L^T, every prox sub-step with project_on_kernel, the offline P / K products,
+    lambda_max and 20 CP iterations (max_iters = 19, tol = 0) with the final iterate."""
+    gen_ops(out, WIDE, seed=21)
+    gen_prox(out, WIDE, seed=22)
+    for name, rf in WIDE:
+        r = rf()
+        run_chock(name, r, 19, 0.0, out)
+        tree = core.MarkovChainScenarioTreeFactory(r["P"], r["v"], r["N"], r["tau"]).create()
+        out.update(tree_arrays(name, tree))
+        # the per-node offline products of every nonleaf node and every sixth leaf (the leaves' are sqrtPf' sqrtPf
+        # over and over; all of them would take the file past a committed file's size)
+        m = tree.num_nonleaf_nodes
+        keep = np.concatenate([np.arange(m), np.arange(m, tree.num_nodes, 6)])
+        out[f"{name}/off_nodes"] = keep
+        for key in ("off_P", "off_Abar", "off_K"):
+            full = out[f"{name}/{key}"]
+            out[f"{name}/{key}"] = full[keep[keep < full.shape[0]]]
+
+
 def gen_trees(out):
     rng = np.random.default_rng(5)
     p3 = np.array([[0.1, 0.8, 0.1], [0.4, 0.6, 0], [0, 0.3, 0.7]])
@@ -480,6 +534,11 @@ def main():
         g = {}
         gen_general(g)
         np.savez_compressed(os.path.join(OUT, "general_kat.npz"), **g)
+        return
+    if sys.argv[1:] == ["wide"]:  # only the wide trees' fixture
+        g = {}
+        gen_wide(g)
+        np.savez_compressed(os.path.join(OUT, "wide_kat.npz"), **g)
         return
     ops = {}
     gen_ops(ops)

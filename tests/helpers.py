@@ -32,13 +32,16 @@ def crafted_rotations(op):
     return 1 if ok else 3
 
 
-def crafted_start(op, alpha, seed, T=50.0, rot=0):
+def crafted_start(op, alpha, seed, T=50.0, rot=0, calm=False):
     """(p0, d0) of a warm start whose first CP iteration takes every branch of the dual step:
     p0 standard normal on the live primal slots, d0 = alpha * standard normal on the live dual
     slots (zero on the placeholders, like every iterate the loop produces); every child cone
     and, by an independent shuffle, every leaf cone gets a class from a balanced seeded
     assignment: identity sets the cone's t entry (eta6 / eta13) of d0 to +alpha T, zero to
     -alpha T, scaling keeps the random value. rot rotates the classes (crafted_rotations).
+    calm: a scaling cone's t entry of d0 is 0 instead, so that the t the iteration projects is the
+    primal's half alone and stays clear of +-|F| on trees with hundreds of small cones, where some
+    random t lands within the census margin of an edge for every seed.
     Returns (p0, d0, child classes in the order of op.kids, leaf classes in that of op.leaves)."""
     rng = np.random.default_rng(seed)
     pm, dm = op.live_masks()
@@ -49,6 +52,8 @@ def crafted_start(op, alpha, seed, T=50.0, rot=0):
     for nodes, E, cls in ((op.kids, op.E6, ccls), (op.leaves, op.E13, lcls)):
         d0[E[nodes[cls == 0]]] = alpha * T
         d0[E[nodes[cls == 1]]] = -alpha * T
+        if calm:
+            d0[E[nodes[cls == 2]]] = 0.0
     return p0, d0, ccls, lcls
 
 

@@ -39,7 +39,7 @@ def _lp(Z, p, alpha):
 
 
 def _cases():
-    """Seeded cases: c = 1 .. 6, every alpha of ALPHAS, random outcomes, ties (outcomes drawn from
+    """Seeded cases: c = 1 .. 6 and 17, 65, 82, every alpha of ALPHAS, random outcomes, ties (outcomes drawn from
     three values, all equal) and probabilities as small as 1e-12."""
     rng = np.random.default_rng(20240)
     out = []
@@ -54,6 +54,24 @@ def _cases():
                 p = rng.random(c) + 0.05
                 if kind == "tiny_p" and c > 1:
                     p[rng.integers(c)] = 1e-12
+                p /= p.sum()
+                out.append((Z, p, alpha))
+    # wide families (17, 65 and 82 outcomes, the child counts of branch_cases.WIDE), drawn after the
+    # cases above so that those keep their values: the same kinds, and a child of probability zero
+    for c in (17, 65, 82):
+        for alpha in ALPHAS:
+            for kind in ("random", "ties", "equal", "tiny_p", "zero_p"):
+                Z = rng.standard_normal(c) * 3.0
+                if kind == "ties":
+                    Z = rng.choice(np.array([-1.5, 0.25, 2.0]), size=c)
+                elif kind == "equal":
+                    Z = np.full(c, float(rng.standard_normal()))
+                p = rng.random(c) + 0.05
+                if kind == "tiny_p":
+                    p[rng.integers(c)] = 1e-12
+                elif kind == "zero_p":
+                    p[int(np.argmax(Z))] = 0.0  # the worst outcome cannot happen
+                    p[rng.integers(c)] = 0.0
                 p /= p.sum()
                 out.append((Z, p, alpha))
     return out

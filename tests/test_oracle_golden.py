@@ -267,3 +267,83 @@ def test_general_oracle_trajectories(golden, name):
     assert trace_rel_err(derr, z[f"{name}/cp_delta_error"]) <= 1e-8
     assert rel_err(zf, z[f"{name}/cp_z"]) <= 1e-9
     assert rel_err(ef, z[f"{name}/cp_eta"]) <= 1e-9
+
+
+# ---------------------------------------------------------------- wide branching
+# 8 children per node at (5, 3) and 1 .. 12 at (17, 5) (tests/branch_cases.py "w8s" and "r12"): the
+# problems above have at most three children per node, so the oracle is pinned on wide ones before
+# any kernel is held to it there, at this file's bounds.
+WIDE = ["w8s", "r12"]
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_wide_recipe_and_tree_are_the_fixtures(golden, name):
+    """branch_cases' recipe (restated in gen_golden.py) gives the stored recipe bit for bit, and the
+    tree factory the reference's tree: ancestors, stages, values, probabilities, children, exact."""
+    import branch_cases as bc
+    z = golden("wide_kat")
+    r, orc = _oracle(z, name)
+    mine = bc._wide_recipe(name, False)
+    for k, val in mine.items():
+        assert np.array_equal(np.asarray(val), np.asarray(r[k])), k
+    tree = core.MarkovChainScenarioTreeFactory(r["P"], r["v"], r["N"], r["tau"]).create()
+    n, m = tree.num_nodes, tree.num_nonleaf_nodes
+    assert n == z[f"{name}/tree_anc"].size == bc.WIDE_NODES.get(name, 73) and m == int(z[f"{name}/tree_num_nonleaf"])
+    assert np.array_equal([tree.ancestor_of(i) for i in range(n)], z[f"{name}/tree_anc"])
+    assert np.array_equal([tree.stage_of(i) for i in range(n)], z[f"{name}/tree_stage"])
+    assert np.array_equal([tree.value_at_node(i) for i in range(n)], z[f"{name}/tree_value"])
+    assert np.array_equal(np.asarray(tree._ScenarioTree__probability, dtype=float), z[f"{name}/tree_prob"])
+    assert np.array_equal(np.concatenate([np.asarray(tree.children_of(i)) for i in range(m)]), z[f"{name}/tree_children"])
+    assert np.array_equal(np.concatenate([tree.conditional_probabilities_of_children(i) for i in range(m)]), z[f"{name}/tree_cond_prob"])
+    nch = np.array([len(tree.children_of(i)) for i in range(m)])
+    assert (nch.min(), nch.max()) == ((8, 8) if name == "w8s" else (1, 12)) and (name == "w8s" or set(nch) == set(range(1, 13)))
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_wide_oracle_ell_matches_reference(golden, name):
+    z = golden("wide_kat")
+    r, orc = _oracle(z, name)
+    assert orc.P == z[f"{name}/ops_z"].size and orc.D == z[f"{name}/ops_eta"].size
+    assert rel_err(orc.ell(z[f"{name}/ops_z"]), z[f"{name}/ops_Lz"]) <= 1e-13
+    assert rel_err(orc.ell_t(z[f"{name}/ops_eta"]), z[f"{name}/ops_LTeta"]) <= 1e-13
+    out_d = orc.ell(z[f"{name}/ops_z"], template=z[f"{name}/ops_tmpl_dual"])
+    assert rel_err(out_d, z[f"{name}/ops_ell_out"]) <= 1e-13
+    out_p = orc.ell_t(z[f"{name}/ops_eta"], template=z[f"{name}/ops_tmpl_primal"])
+    assert rel_err(out_p, z[f"{name}/ops_ellT_out"]) <= 1e-13
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_wide_oracle_prox_steps_match_reference(golden, name):
+    """The offline P / K / Abar products (every nonleaf node, every sixth leaf), the dynamics and kernel
+    projections, prox f, prox g* and its steps."""
+    z = golden("wide_kat")
+    r, orc = _oracle(z, name)
+    P, K, Abar = orc.offline_per_node()
+    keep = z[f"{name}/off_nodes"]
+    assert rel_err(P[keep], z[f"{name}/off_P"]) <= 1e-12 and rel_err(K[:orc.m], z[f"{name}/off_K"]) <= 1e-12
+    assert rel_err(Abar[keep][1:], z[f"{name}/off_Abar"][1:]) <= 1e-12
+    alpha = float(z[f"{name}/prox_alpha"])
+    zin, ein, x0 = z[f"{name}/prox_z"], z[f"{name}/prox_eta"], r["x0"]
+    assert rel_err(orc.project_on_dynamics(zin, x0), z[f"{name}/prox_dyn"]) <= 1e-11
+    assert rel_err(orc.project_on_kernel(zin), z[f"{name}/prox_kernel"]) <= 1e-12
+    assert rel_err(orc.prox_f(zin, alpha, x0), z[f"{name}/prox_f"]) <= 1e-11
+    assert rel_err(orc.modify_dual_add_halves(ein, alpha), z[f"{name}/prox_modify_halves"]) <= 1e-14
+    assert rel_err(orc.project_on_constraints_nonleaf(ein), z[f"{name}/prox_proj_nonleaf"]) <= 1e-14
+    assert rel_err(orc.project_on_constraints_leaf(ein), z[f"{name}/prox_proj_leaf"]) <= 1e-14
+    assert rel_err(orc.prox_gconj(ein, alpha), z[f"{name}/prox_gconj"]) <= 1e-13
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_wide_oracle_trajectories(golden, name):
+    """lambda_max and 20 CP iterations at the fixture's step size: traces and the final iterate."""
+    z = golden("wide_kat")
+    r, orc = _oracle(z, name)
+    assert int(z[f"{name}/cp_max_iters"]) == 19
+    lam, _ = orc.step_size()
+    assert abs(lam - float(z[f"{name}/cp_lambda"])) <= 1e-10 * lam
+    st, err, derr, zf, ef, _ = orc.chock(r["x0"], 19, float(z[f"{name}/cp_tol"]), alpha=float(z[f"{name}/cp_alpha"]))
+    assert st == int(z[f"{name}/cp_status"]) and err.shape == (20, 3)
+    assert trace_rel_err(err, z[f"{name}/cp_error"]) <= 1e-8
+    assert trace_rel_err(derr, z[f"{name}/cp_delta_error"]) <= 1e-8
+    assert rel_err(zf, z[f"{name}/cp_z"]) <= 1e-9
+    assert rel_err(ef, z[f"{name}/cp_eta"]) <= 1e-9

@@ -6,7 +6,9 @@ top's cut, LDS bytes, widest stage, F-in-LDS and fold choices, and per tier its 
 widest level, LDS bytes of both kernels, F mode and fold) with expected values written into the
 program: binary N = 12 at 20 / 8 (config 2) with fold allowed, fold disallowed and per-stage
 forced; branching 4, N = 5 at 20 / 8; binary N = 3 at 3 / 2 (all of it lands in the top); binary
-N = 4 at 64 / 32 (F per level); binary N = 4 at 96 / 48 (nothing fits: cut 0).
+N = 4 at 64 / 32 (F per level); binary N = 4 at 96 / 48 (nothing fits: cut 0). Trees with more than
+four children per node (5-ary, 8-ary, ragged, a root of 82) have no recorded plan: the program checks
+that the top and the tiers tile the parent stages exactly once, or that the planner declines.
 
 Where the expected numbers come from: the planning block of raocp_ctx_create as it stood before
 the planner was split out (the commit before this file was added), lifted unchanged into a
@@ -35,3 +37,6 @@ def test_tier_plans_match_recorded_plans(tmp_path):
     print(p.stdout)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "0 of 7 plans differ" in p.stdout
+    # 5-ary, 8-ary, ragged (1 .. 12 and 1 .. 6 children) and wide-root stage profiles: every parent stage
+    # in exactly one tier, or the planner declines (plan_host_main.cpp: covers)
+    assert "0 of 6 wide profiles broken" in p.stdout and "BROKEN" not in p.stdout

@@ -89,6 +89,61 @@ bool run(const Case& cs) {
     return ok;
 }
 
+// Wide and ragged stage profiles (more than four children): no recorded plan, the property instead.
+// Either the planner declines (cut = 0: the per-stage kernels) or the top [0, cut) and the tiers, the
+// shallowest first, tile the parent stages [0, N) with no gap and no overlap, every tier non-empty,
+// its widest level within the tree's widest stage, and every launch within the LDS budget.
+// kids[s](q): the child count of the q-th node of stage s.
+template <class Kids>
+bool covers(const char* name, int N, const raocp::TierSizes& z, Kids kids) {
+    std::vector<int> stage_ptr(N + 2), ch_start, nch, cls_ptr(N + 1), pair_ptr(N + 1);
+    int n = 0, cnt = 1, cmax = 0, widest = 1;
+    for (int s = 0; s <= N; ++s) {
+        stage_ptr[s] = n;
+        int next = 0;
+        if (s < N)
+            for (int q = 0; q < cnt; ++q) {
+                const int c = kids(s, q);
+                ch_start.push_back(n + cnt + next);
+                nch.push_back(c);
+                next += c;
+                cmax = c > cmax ? c : cmax;
+            }
+        n += cnt;
+        if (s < N) cnt = next;
+        widest = cnt > widest ? cnt : widest;
+    }
+    stage_ptr[N + 1] = n;
+    for (int s = 0; s <= N; ++s) {
+        cls_ptr[s] = s;          // one class per stage
+        pair_ptr[s] = cmax * s;  // one pair per child slot of each class
+    }
+    const raocp::TierTree tr{n, N, stage_ptr.data(), ch_start.data(), nch.data(), cls_ptr.data(), pair_ptr.data(), cmax};
+    const raocp::TierLimits lim{31, 62};
+    bool ok = true;
+    for (int fold = 0; fold < 2; ++fold) {
+        const raocp::TierPlanResult got = raocp::plan_tiers(tr, z, lim, 256, fold != 0, false);
+        bool good = true;
+        if (got.cut == 0) {
+            good = got.tiers.empty();
+        } else {
+            int at = got.cut;
+            good = got.cut >= 1 && got.cut <= N && got.lds_top <= raocp::kTierLds && got.maxch_top <= widest;
+            for (const auto& t : got.tiers) {
+                good = good && t.s0 == at && t.s1 > t.s0 && t.s1 <= N && t.maxch >= 1 && t.maxch <= widest &&
+                       t.lds_b <= raocp::kTierLds + 2048 && t.lds_f <= raocp::kTierLds + 2048;
+                at = t.s1;
+            }
+            good = good && at == N;
+        }
+        printf("%s fold_ok=%d: N=%d n=%d cmax=%d nx=%d nu=%d: %s\n", name, fold, N, n, cmax, z.nx, z.nu,
+               good ? (got.cut ? "covers" : "declines") : "BROKEN");
+        print("got ", got);
+        ok = ok && good;
+    }
+    return ok;
+}
+
 }  // namespace
 
 int main() {
@@ -117,5 +172,14 @@ int main() {
     int bad = 0;
     for (const Case& cs : cases) bad += run(cs) ? 0 : 1;
     printf("%d of %zu plans differ\n", bad, cases.size());
-    return bad ? 1 : 0;
+    const raocp::TierSizes z5{5, 3, 8, 8, 4, 10, 10, 10, 6}, z17{17, 5, 24, 24, 6, 24, 26, 26, 8};
+    int broken = 0;
+    broken += covers("five3", 3, z5, [](int, int) { return 5; }) ? 0 : 1;      // 156 nodes
+    broken += covers("five6", 6, z20, [](int, int) { return 5; }) ? 0 : 1;     // 19,531 nodes: tiers below a top
+    broken += covers("eight2", 2, z20, [](int, int) { return 8; }) ? 0 : 1;    // 73 nodes
+    broken += covers("ragged2", 2, z17, [](int s, int q) { return s == 0 ? 12 : 1 + (7 * q) % 12; }) ? 0 : 1;  // 91 nodes
+    broken += covers("ragged4", 4, z20, [](int s, int q) { return 1 + (7 * q + s) % 6; }) ? 0 : 1;
+    broken += covers("root82", 2, z5, [](int s, int) { return s == 0 ? 82 : 2; }) ? 0 : 1;  // 247 nodes
+    printf("%d of 6 wide profiles broken\n", broken);
+    return bad || broken ? 1 : 0;
 }
